@@ -10,9 +10,9 @@ value = (windows x timed iterations) / wall time of the timed region, max over r
 scaling at 8 GPUs on batched independent windows"): the job is a fixed batch of --windows
 independent windows (2,048 by default) split across the ranks, one process per GPU and no
 data-path collective. --windows-per-gpu W instead gives every rank its own W
-windows (weak scaling, distinct seeds across ranks). At the end of the
-run the per-window summaries and final poses are all-gathered to rank 0 over RCCL (§8e), outside
-the timed region, and rank 0 checks that every window of the job ran every iteration.
+windows (weak scaling, distinct seeds across ranks). With --full or --dump-outputs the per-window
+summaries and final poses are all-gathered to rank 0 over RCCL at the end of the run (§8e), outside
+the timed region, and with --full rank 0 checks that every window of the job ran every iteration.
 
 `--gpus N` without a launcher starts N ranks itself: a `torch.distributed.run` child process
 (this process never touches the GPU), one rank per GPU, 127.0.0.1 rendezvous.
@@ -20,8 +20,20 @@ the timed region, and rank 0 checks that every window of the job ran every itera
 All tolerances are set to 0 so every timed iteration does real work (the K-iteration protocol of
 BASELINE.md); inputs are resident in HBM before the timed region.
 
-Also reported (rank 0): the single-window latency mode (the reference's own use: one window per
-::ceres::Solve) — resident iters/s and the end-to-end set_problems + solve wall time; per-kernel
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure needs:
+it generates the seeded windows, uploads them, runs W warm-up and N timed iterations, fetches the
+solve's results and prints the result line (`value`, `ms_per_step` = wall milliseconds of one timed
+step). `--dump-outputs DIR` then writes what that solve returned to its caller (the per-window
+summaries and the written-back poses, speed/biases and landmarks) as DIR/<name>.npy in float64,
+64 MB at most (a fixed sample of the landmarks, and of the windows of a very large job), so that
+two builds can be compared output for output: the inputs depend on the arguments only.
+
+Everything below is measured by `--full` only (rank 0), each leg with runs of its own; `--no-cpu`,
+`--no-latency` and `--no-profile` drop single legs of it. The single-window and CPU legs run
+min(--steps, 20) timed iterations after min(--warmup, 5) warm-up ones (`full_legs` in the result
+line), so that a long headline run does not multiply their cost. The legs: the end-of-run gather check, the
+per-solve rate including the PCIe transfers; the single-window latency mode (the reference's own
+use: one window per ::ceres::Solve) — resident iters/s and the end-to-end set_problems + solve wall time; per-kernel
 device time of one iteration (HIP events on the context's stream); the roofline of the dominant
 kernel against both the builder's byte model and SURVEY.md §8(d)'s compulsory bytes, plus the
 whole-iteration §8(d) HBM fraction; accuracy (ATE of window 0 vs ground truth for GPU and CPU
@@ -339,10 +351,49 @@ def parse_args(argv=None):
     ap.add_argument("--kernel-reps", type=int, default=5, help="repetitions per kernel in the roofline table")
     ap.add_argument("--e2e-reps", type=int, default=5, help="single-window set_problems + solve repetitions")
     ap.add_argument("--cholesky-schedule", type=int, default=0, help="0 auto, 1 persistent per window, 2 tile-parallel, 3 persistent split over a nested-dissection window, 4 pipelined persistent (two teams per window), 5 split with each part pipelined")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-latency", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: gather check, per-solve rate incl. PCIe, "
+                         "single-window latency, per-kernel roofline, CPU baseline and accuracy")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed solve returned (summaries, poses, speed/biases, landmarks) as "
+                         "DIR/<name>.npy, float64, at most 64 MB in all")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: without the CPU baseline and accuracy")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: without the single-window mode")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: without the per-kernel roofline")
     return ap.parse_args(argv)
+
+
+FULL_LEG_STEPS, FULL_LEG_WARMUP = 20, 5  # --full: iteration cap of the legs beyond the headline run
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000     # --dump-outputs: all files together stay below this
+DUMP_LANDMARK_BYTES = 32 * 1000 * 1000   # the landmarks' share of it (the largest output by far)
+
+
+def dump_plan(n_windows, cfg):
+    """Which part of the job's results --dump-outputs keeps, from the arguments alone (every rank
+    and every run computes the same): (window_index, landmark_index), each sorted, or None = all.
+    The landmarks are the large output (S50: 64 kB per window), so every window keeps the same
+    seeded subset of its landmarks; a job so large that even the poses and speed/biases would
+    exceed their share keeps a seeded subset of its windows."""
+    rng = np.random.default_rng(SEED0)
+    small = 8 * (cfg["n_kf"] * (7 + 9) + len(SUMMARY_COLS) + 1)      # bytes per window without landmarks
+    n_win = min(n_windows, (DUMP_BUDGET_BYTES - DUMP_LANDMARK_BYTES) // 2 // small)
+    win_idx = None if n_win == n_windows else np.sort(rng.choice(n_windows, n_win, replace=False))
+    n_lm = min(cfg["n_lm"], max(1, DUMP_LANDMARK_BYTES // (n_win * 4 * 8)))
+    lm_idx = None if n_lm == cfg["n_lm"] else np.sort(rng.choice(cfg["n_lm"], n_lm, replace=False))
+    return win_idx, lm_idx
+
+
+def dump_outputs(path, arrays):
+    """Write {name: array} as path/<name>.npy (float64) and check the size limit."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_BUDGET_BYTES, total
+    return total
 
 
 def single_window(og, cfg, opts, args, device):
@@ -517,22 +568,43 @@ def main(argv=None):
     sums = ctx.solve_end()
     elapsed = t1 - t0
     early = sum(1 for s in sums if s["num_iterations"] < total_iters)
-    gn_frac = float(np.mean([(s["num_successful_steps"] - 1) / max(1, s["num_iterations"]) for s in sums]))
     elapsed, early = aggregate(dist, elapsed, early, device)
 
     # ---- §8e end-of-run gather (outside the timed region): summaries + final poses to every rank
-    g0 = time.perf_counter()
-    all_sums = gather_rows(dist, summary_rows(mine, sums), args.windows, device)
-    all_poses = gather_rows(dist, np.stack([w.poses().reshape(-1) for w in windows]), args.windows, device)
-    gather_s = time.perf_counter() - g0
+    if args.full or args.dump_outputs:
+        g0 = time.perf_counter()
+        all_sums = gather_rows(dist, summary_rows(mine, sums), args.windows, device)
+        all_poses = gather_rows(dist, np.stack([w.poses().reshape(-1) for w in windows]), args.windows, device)
+        gather_s = time.perf_counter() - g0
 
-    # per-solve rate including the PCIe upload of the parameters and the write-back (not `value`)
-    for w in windows:
-        w.reset()
-    ctx.synchronize()
-    a = time.perf_counter()
-    ctx.solve(opts)  # okvisgpu_solve uploads the parameters itself
-    pcie_s = time.perf_counter() - a
+    # ---- --dump-outputs: what the timed solve wrote back to its caller (before anything resets it)
+    if args.dump_outputs:
+        win_idx, lm_idx = dump_plan(args.windows, cfg)
+        lm_sel = slice(None) if lm_idx is None else lm_idx
+        all_sbs = gather_rows(dist, np.stack([w.speed_biases().reshape(-1) for w in windows]), args.windows, device)
+        all_lms = gather_rows(dist, np.stack([w.landmarks()[lm_sel].reshape(-1) for w in windows]), args.windows,
+                              device)
+        if rank == 0:
+            win_sel = slice(None) if win_idx is None else win_idx
+            out = {"summary": all_sums[win_sel],
+                   "poses": all_poses[win_sel].reshape(-1, cfg["n_kf"], 7),
+                   "speed_biases": all_sbs[win_sel].reshape(-1, cfg["n_kf"], 9),
+                   "landmarks": all_lms[win_sel].reshape(len(all_sums[win_sel]), -1, 4)}
+            if win_idx is not None:
+                out["window_index"] = win_idx
+            if lm_idx is not None:
+                out["landmark_index"] = lm_idx
+            dump_outputs(args.dump_outputs, out)
+
+    if args.full:
+        gn_frac = float(np.mean([(s["num_successful_steps"] - 1) / max(1, s["num_iterations"]) for s in sums]))
+        # per-solve rate including the PCIe upload of the parameters and the write-back (not `value`)
+        for w in windows:
+            w.reset()
+        ctx.synchronize()
+        a = time.perf_counter()
+        ctx.solve(opts)  # okvisgpu_solve uploads the parameters itself
+        pcie_s = time.perf_counter() - a
 
     value = args.windows * args.steps / elapsed
     result = {
@@ -558,9 +630,22 @@ def main(argv=None):
         },
     }
 
+    # The --full legs below time solves of their own. Their cost grows with the iteration count
+    # (the CPU oracle runs ~100 S50 iterations/s, the IMU re-integration census solves 0..K
+    # iterations: K^2), so they run at most FULL_LEG_STEPS timed iterations after FULL_LEG_WARMUP
+    # warm-up ones whatever --steps asks of the headline run: a --full run stays within minutes.
+    leg = argparse.Namespace(**vars(args))
+    leg.steps, leg.warmup = min(args.steps, FULL_LEG_STEPS), min(args.warmup, FULL_LEG_WARMUP)
+    leg_iters = leg.warmup + leg.steps
+    leg_opts = bench_options(leg_iters)
+    leg_opts.cholesky_schedule = args.cholesky_schedule
     if args.cpu_iters is None:
-        args.cpu_iters = total_iters
-    if rank == 0:
+        args.cpu_iters = leg_iters
+    if rank == 0 and not args.full:
+        result["early_terminated_windows"] = early
+        result["problem_stats_per_gpu"] = stats
+        print(json.dumps(result), flush=True)
+    if rank == 0 and args.full:
         ran_k = bool(np.all(all_sums[:, 3] == total_iters)) and len(all_sums) == args.windows
         result["gather"] = {
             "windows": int(len(all_sums)), "all_windows_ran_k_iterations": ran_k,
@@ -573,10 +658,11 @@ def main(argv=None):
         result["per_solve_incl_pcie"] = {"wall_s": pcie_s, "iterations": total_iters,
                                          "window_iterations_per_s": len(windows) * total_iters / pcie_s}
         result["frac_iterations_with_gn_solve"] = gn_frac
+        result["full_legs"] = {"steps": leg.steps, "warmup": leg.warmup, "cpu_iters": args.cpu_iters}
         result["problem_stats_per_gpu"] = stats
         # ---- single-window latency mode (1 window, this GPU): the reference's own use
         if not args.no_latency:
-            sw, gpu_pose_w0, gt_p = single_window(og, cfg, opts, args, local_rank)
+            sw, gpu_pose_w0, gt_p = single_window(og, cfg, leg_opts, leg, local_rank)
             result["single_window"] = sw
             result["single_window_iters_per_s"] = sw["iters_per_s"]
         # ---- roofline: per-kernel device time on the resident batch, dominant kernel by time
@@ -648,7 +734,7 @@ def main(argv=None):
                 "host": {"cpu_model": cpu_model(), "host_threads": allc, "nproc": os.cpu_count()},
                 "variants": variants,
             }
-            if not args.no_latency and args.cpu_iters == total_iters:
+            if not args.no_latency and args.cpu_iters == leg_iters:
                 P0 = wc.poses()
                 result["accuracy"] = {
                     "ate_gpu_m": ate(gpu_pose_w0, gt_p), "ate_cpu_m": ate(P0, gt_p),

@@ -1,6 +1,6 @@
 """rocprofv3 kernel_trace.csv -> per (kernel, grid size) launch count and mean duration, so the
 batched launches can be compared with bench.py's event-timed roofline entry. last5_us = mean of the
-group's last 5 dispatches: in a bench.py run those are the roofline table's okvisgpu_time_kernel
+group's last 5 dispatches: in a bench.py --full run those are the roofline table's okvisgpu_time_kernel
 repetitions (every window armed), which is what the bench's roofline.ms_per_iteration times."""
 import collections
 import csv

@@ -11,7 +11,7 @@ if [ "$2" = "test" ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $OUT/pytest.txt 2>&1 || { echo "pytest rc=$?"; tail -30 $OUT/pytest.txt; exit 1; }
   tail -2 $OUT/pytest.txt
 fi
-timeout -k 10 600 python bench.py --no-cpu --no-latency --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err || { echo "bench rc=$?"; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full --no-cpu --no-latency --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err || { echo "bench rc=$?"; tail -20 $OUT/bench.err; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])
 print('value', round(d['value']), 'ms/it', round(d['ms_per_step'],3))

@@ -36,11 +36,11 @@ def test_facade_cpu(consumers):
     assert "facade_test cpu ok" in r.stdout
 
 
-def test_header_is_plain_c():
+def test_header_is_plain_c(tmp_path):
     """The C ABI header compiles as C99 and as C++11 on its own (-pedantic -Werror)."""
     src = "#include \"okvisgpu.h\"\nint main(void) { okvisgpu_options o; okvisgpu_problem p; (void)o; (void)p; return 0; }\n"
     for cc, std, ext in (("gcc", "-std=c99", ".c"), ("g++", "-std=c++11", ".cpp")):
-        path = os.path.join("/tmp", "okvisgpu_hdr" + ext)
+        path = str(tmp_path / ("okvisgpu_hdr" + ext))
         with open(path, "w") as f:
             f.write(src)
         r = subprocess.run([cc, std, "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I",
