@@ -490,6 +490,20 @@ int okvisgpu_get_stats(okvisgpu_ctx* ctx, okvisgpu_problem_stats* stats);
 int okvisgpu_plan_window(const okvisgpu_problem* problem, int32_t nested_dissection, int64_t* info,
                          uint8_t* tile_nz, int32_t* step_launch, int32_t* natural);
 
+/* Host-only digest of a batch's plan on a device of cu_count compute units (no device, no context;
+ * development: pins the planner's output bit for bit, tests/test_plan_digest.py). Any output may be
+ * NULL.
+ *   totals[16]:  f_total, s_total, linv_total, fwd_total, defer_total, max_fpad, max_panels,
+ *                n_chol_launches, n_panels, n_band_updates, n_band_updates_diag, any_split, obs_iso,
+ *                bytes of the uploaded region, bytes of the scratch region, 0
+ *   *n_entries:  device arrays of the arena table; per entry i < min(capacity, *n_entries), in
+ *                table order: names[32 * i] (NUL-terminated), region[i] (0 uploaded, 1 scratch),
+ *                bytes[i], hash[i] = FNV-1a-64 of the uploaded bytes (0 for scratch)
+ * Size the arrays from a first call with capacity 0. */
+int okvisgpu_plan_digest(const okvisgpu_problem* problems, int32_t n_windows, int32_t cu_count, int64_t* totals,
+                         int32_t capacity, int32_t* n_entries, char* names, int32_t* region, int64_t* bytes,
+                         uint64_t* hash);
+
 /* Copy device parameter values back into the caller's host arrays without solving. */
 int okvisgpu_get_params(okvisgpu_ctx* ctx);
 

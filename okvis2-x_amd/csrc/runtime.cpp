@@ -2,18 +2,14 @@
 //
 // The drop-in replacement for `::ceres::Solve(options_, problem_.get(), &summary_)` in
 // okvis::ViGraph::optimise (okvis_ceres/src/ViGraph.cpp:1844-1890): structure analysis of each
-// window (residual blocks, constant flags, Schur ordering with landmarks as e-blocks, the
-// reduced-system contribution lists), one HBM arena per context, upload, and the trust-region
+// window and the arena layout (plan.cpp), one HBM arena per context, upload, and the trust-region
 // iteration as a captured hipGraph that is replayed max_num_iterations times with every decision
 // taken on the device (kernels_control.hip). The host synchronises once per solve (plus once per
 // iteration only when a CeresIterationCallback-style time limit is requested).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
-#include <cfloat>
 #include <chrono>
-#include <climits>
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
@@ -23,7 +19,6 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <numeric>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -32,7 +27,9 @@
 #include "../../include/okvisgpu.h"
 #include "device_problem.hpp"
 #include "launch.hpp"
+#include "loss.hpp"
 #include "okvisgpu_math.hpp"
+#include "plan.hpp"
 
 using namespace okg;
 
@@ -50,13 +47,6 @@ struct HipError {
       throw HipError{std::string(#x) + ": " + hipGetErrorString(e_),                          \
                      e_ == hipErrorOutOfMemory ? OKVISGPU_ERR_OUT_OF_MEMORY : OKVISGPU_ERR_DEVICE}; \
   } while (0)
-
-struct ArgError {
-  std::string msg;
-};
-struct UnsupportedError {
-  std::string msg;
-};
 
 double nowS() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -86,1330 +76,15 @@ void forWindows(int n, F&& fn) {
   for (auto& x : th) x.join();
 }
 
-// Host mirror of everything uploaded (built by analyse()).
-struct HostBatch {
-  int n_win = 0;
-  std::vector<const okvisgpu_problem*> probs;
-  // bases per window
-  std::vector<int> pose_base, sb_base, lm_base, cam_base, obs_base, imu_base, pp_base, sbp_base, rp_base, sample_base;
-  // parameters (initial copies)
-  std::vector<double> pose, sb, lm, extr, cam;
-  std::vector<int32_t> lm_perm;  // internal landmark k of window w is the caller's landmark lm_perm[lm_base[w] + k]
-  // extrinsics: camera c of window w is pose-kind block cam_pose[cam_base[w] + c] (after the states)
-  std::vector<int32_t> cam_pose;
-  std::vector<uint8_t> win_ext_free;  // window has a variable extrinsics block (write-back)
-  // extrinsic visits (landmark, variable camera): observation lists (global obs index), the group's
-  // range, segment slots; pose-extrinsics cross blocks (state pose, variable camera) with their obs
-  std::vector<int32_t> xvisit_pose, xvisit_lm, xvisit_obs_begin, xvisit_obs, xvisit_slot, lmg_xbegin;
-  std::vector<int32_t> pe_pose, pe_ext, pe_obs_begin, pe_obs;
-  std::vector<int32_t> pose_win, sb_win, lm_win, pose_f, sb_f;
-  std::vector<uint8_t> lm_free, pose_active, sb_active;
-  // obs (sorted) + permutation to the caller's order (within the window)
-  std::vector<int32_t> obs_pose, obs_lm, obs_cam, obs_win, obs_orig;
-  std::vector<uint8_t> obs_flags;
-  std::vector<double> obs_kp, obs_L;
-  std::vector<double> obs_Ls;  // isotropic batches: L = diag(s, s) per observation, s only (obs_iso)
-  bool obs_iso = false;
-  // visits
-  std::vector<int32_t> lm_visit_begin, visit_pose, visit_obs_begin, visit_lm, lmg_begin;
-  std::vector<int32_t> lmg_info;  // [n_lmg+1][kLmgInfo]: first landmark, first visit, window, first segment,
-                                  // first partial block, first landmark-pair product
-  // visit segments: per landmark group, the visits of one free pose (k_lm_visit pre-sums them)
-  std::vector<int32_t> seg_gbegin, seg_pose, seg_range, visit_slot;
-  // partial Schur blocks: per landmark group and pose pair, sum of Z_a Z_b^T over the group's landmarks
-  std::vector<int32_t> part_gbegin, part_cbegin, part_contrib;
-  // imu
-  std::vector<int32_t> imu_blocks, imu_win, imu_sbegin;
-  std::vector<uint8_t> imu_flags;
-  std::vector<int64_t> imu_t0, imu_t1, imu_ts;
-  std::vector<double> imu_ga, imu_par, imu_state;
-  // host-evaluated factors (ABI 5): global factor index n_imu_total + h, after every IMU factor;
-  // slot[k] = IMU-layout slot (0 pose0, 1 sb0, 2 pose1, 3 sb1) of the functor's k-th block
-  struct HostFactor { int win, local, np, dim; int8_t slot[4]; okvisgpu_loss loss; };
-  int n_imu_total = 0;
-  std::vector<HostFactor> hf;
-  std::vector<int32_t> host_blocks, host_win, win_host_range;
-  std::vector<uint8_t> host_flags;
-  // priors
-  std::vector<int32_t> pp_block, pp_win, sbp_block, sbp_win;
-  std::vector<double> pp_meas, pp_L, sbp_meas, sbp_L;
-  // relative-pose edges
-  std::vector<int32_t> rp_blocks, rp_win;
-  std::vector<uint8_t> rp_flags, rp_kind;
-  std::vector<double> rp_dx, rp_J, rp_lp;
-  // reduced structure
-  std::vector<int32_t> win_foff, win_fdim, win_fpad;
-  std::vector<int64_t> win_soff, win_linvoff, win_fwdoff;
-  std::vector<int32_t> win_lmg_range;
-  std::vector<int32_t> win_pose_range, win_sb_range, win_lm_range, win_obs_range, win_imu_range, win_pp_range,
-      win_sbp_range, win_rp_range;
-  std::vector<int32_t> fb_win, fb_kind, fb_index, fb_off, fb_cbegin;
-  // S offset of every f-block: fb_off, plus the window's gap rows after the left part of a
-  // nested-dissection order (win_sgap: f offset of the gap, gap length; 0 0 without one); natural
-  // index of every f entry (-1: gap row) and natural dimension per window
-  std::vector<int32_t> win_sgap, f_nat, win_fnat, win_bsplit;
-  std::vector<int64_t> win_defoff;
-  int64_t defer_total = 0;
-  bool any_split = false;
-  bool nd = false;  // order the windows' states for the tile-parallel schedule (nested dissection)
-  int lmg_visits = kLmGroupVisits, lmg_lms = kLmGroupMax;  // landmark-group bounds (k_lm_visit workgroups)
-  std::vector<int32_t> chol_root_items;  // (w, d, first-root-of-window flag): tiles no update writes
-  int n_chol_launches = 1;
-  std::vector<Contrib> fb_contrib;
-  std::vector<int32_t> pair_win, pair_fi, pair_fj, pair_cbegin, pair_runs;
-  std::vector<int32_t> asm_pp_items, asm_sb_items, asm_ppl_items;
-  std::vector<int32_t> chol_upd_items, chol_upd_begin, tile_items;
-  int64_t n_panels = 0;  // structurally non-zero tiles below the diagonal (panel products)
-  int64_t n_band_updates = 0;
-  int64_t n_band_updates_diag = 0;  // of which symmetric updates of a diagonal tile (SYRK)
-  std::vector<Contrib> pair_contrib;
-  int64_t s_total = 0, linv_total = 0, fwd_total = 0;
-  std::vector<std::vector<uint8_t>> tileNz;
-  std::vector<uint8_t> tile_nz;
-  std::vector<std::vector<int16_t>> tileFu;
-  std::vector<int16_t> tile_fu;
-  std::vector<int64_t> win_tnzoff;
-  std::vector<int> tileT;
-  int f_total = 0;
-  int max_fpad = 0;
-  int max_panels = 0;  // most non-zero tiles below a diagonal tile (panels of one Cholesky step)
-};
-
-template <class T>
-void appendN(std::vector<T>& v, const T* src, size_t n) {
-  if (n) v.insert(v.end(), src, src + n);
-}
-
-// ---- robust losses (okvisgpu.h "robust losses"): ::ceres::LossFunction::Evaluate of the Ceres
-// loss family (ceres-solver >= 2.1 loss_function.cc, restated: CauchyLoss, TukeyLoss, HuberLoss,
-// SoftLOneLoss, ArctanLoss, TolerantLoss), rho[0..2] = rho(s), rho'(s), rho''(s)
-bool lossValid(const okvisgpu_loss& L) {
-  switch (L.kind) {
-    case OKVISGPU_LOSS_NONE: return true;
-    case OKVISGPU_LOSS_TOLERANT: return L.a >= 0.0 && L.b > 0.0 && std::isfinite(L.a) && std::isfinite(L.b);
-    case OKVISGPU_LOSS_CAUCHY: case OKVISGPU_LOSS_TUKEY: case OKVISGPU_LOSS_HUBER: case OKVISGPU_LOSS_SOFTLONE:
-    case OKVISGPU_LOSS_ARCTAN: return L.a > 0.0 && std::isfinite(L.a);
-  }
-  return false;
-}
-
-void lossRho(const okvisgpu_loss& L, double s, double* rho) {
-  const double a = L.a;
-  switch (L.kind) {
-    case OKVISGPU_LOSS_CAUCHY: {
-      const double b = a * a, c = 1.0 / b;
-      const double sum = 1.0 + s * c, inv = 1.0 / sum;
-      rho[0] = b * std::log(sum);
-      rho[1] = std::max(DBL_MIN, inv);
-      rho[2] = -c * (inv * inv);
-      return;
-    }
-    case OKVISGPU_LOSS_TUKEY: {
-      const double a2 = a * a;
-      if (s <= a2) {  // inlier region
-        const double v = 1.0 - s / a2, v2 = v * v;
-        rho[0] = a2 / 3.0 * (1.0 - v2 * v);
-        rho[1] = v2;
-        rho[2] = -2.0 / a2 * v;
-      } else {  // outlier region: constant cost, no gradient
-        rho[0] = a2 / 3.0;
-        rho[1] = 0.0;
-        rho[2] = 0.0;
-      }
-      return;
-    }
-    case OKVISGPU_LOSS_HUBER: {
-      const double b = a * a;
-      if (s > b) {
-        const double r = std::sqrt(s);
-        rho[0] = 2.0 * a * r - b;
-        rho[1] = std::max(DBL_MIN, a / r);
-        rho[2] = -rho[1] / (2.0 * s);
-      } else {
-        rho[0] = s;
-        rho[1] = 1.0;
-        rho[2] = 0.0;
-      }
-      return;
-    }
-    case OKVISGPU_LOSS_SOFTLONE: {
-      const double b = a * a, c = 1.0 / b;
-      const double sum = 1.0 + s * c, t = std::sqrt(sum);
-      rho[0] = 2.0 * b * (t - 1.0);
-      rho[1] = std::max(DBL_MIN, 1.0 / t);
-      rho[2] = -(c * rho[1]) / (2.0 * sum);
-      return;
-    }
-    case OKVISGPU_LOSS_ARCTAN: {
-      const double b = 1.0 / (a * a);
-      const double sum = 1.0 + s * s * b, inv = 1.0 / sum;
-      rho[0] = a * std::atan2(s, a);
-      rho[1] = std::max(DBL_MIN, inv);
-      rho[2] = -2.0 * s * b * (inv * inv);
-      return;
-    }
-    case OKVISGPU_LOSS_TOLERANT: {
-      const double b = L.b, c = b * std::log(1.0 + std::exp(-a / b));
-      const double x = (s - a) / b;
-      if (x > 36.7) {  // 1 + e^x == e^x in double beyond ln(2^53)
-        rho[0] = s - a - c;
-        rho[1] = 1.0;
-        rho[2] = 0.0;
-      } else {
-        const double ex = std::exp(x);
-        rho[0] = b * std::log(1.0 + ex) - c;
-        rho[1] = std::max(DBL_MIN, ex / (1.0 + ex));
-        rho[2] = 0.5 / (b * (1.0 + std::cosh(x)));
-      }
-      return;
-    }
-    default:
-      rho[0] = s;
-      rho[1] = 1.0;
-      rho[2] = 0.0;
-  }
-}
-
-// the loss of host factor h: host_loss (ABI 6), else CauchyLoss(1) where host_cauchy is set
-okvisgpu_loss hostLoss(const okvisgpu_problem* p, int h) {
-  if (p->host_loss) return p->host_loss[h];
-  okvisgpu_loss L{OKVISGPU_LOSS_NONE, 0, 1.0, 0.0};
-  if (p->host_cauchy && p->host_cauchy[h]) L.kind = OKVISGPU_LOSS_CAUCHY;
-  return L;
-}
-
-void validate(const okvisgpu_problem* p, int w) {
-  auto bad = [&](const std::string& m) { throw ArgError{"window " + std::to_string(w) + ": " + m}; };
-  if (p->n_poses < 0 || p->n_speed_biases < 0 || p->n_landmarks < 0 || p->n_observations < 0 || p->n_imu < 0 ||
-      p->n_pose_priors < 0 || p->n_sb_priors < 0 || p->n_cameras < 0 || p->n_relpose < 0)
-    bad("negative count");
-  if (p->n_poses && !p->poses) bad("poses == NULL");
-  if (p->n_speed_biases && !p->speed_biases) bad("speed_biases == NULL");
-  if (p->n_landmarks && !p->landmarks) bad("landmarks == NULL");
-  if (p->n_observations) {
-    if (!p->obs_pose || !p->obs_landmark || !p->obs_camera || !p->obs_keypoint || !p->obs_sqrt_info)
-      bad("observation arrays missing");
-    if (!p->cameras || !p->extrinsics) bad("cameras / extrinsics missing");
-    for (int o = 0; o < p->n_observations; ++o) {
-      if (p->obs_pose[o] < 0 || p->obs_pose[o] >= p->n_poses) bad("obs_pose out of range");
-      if (p->obs_landmark[o] < 0 || p->obs_landmark[o] >= p->n_landmarks) bad("obs_landmark out of range");
-      if (p->obs_camera[o] < 0 || p->obs_camera[o] >= p->n_cameras) bad("obs_camera out of range");
-    }
-  }
-  for (int c = 0; c < p->n_cameras; ++c)
-    if (p->cameras[c].distortion < 0 || p->cameras[c].distortion > 3) bad("unknown distortion model");
-  if (p->n_extrinsics_priors < 0) bad("negative count");
-  if (p->n_extrinsics_priors && (!p->extrinsics_prior_camera || !p->extrinsics_prior_meas || !p->extrinsics_prior_sqrt_info))
-    bad("extrinsics prior arrays missing");
-  for (int i = 0; i < p->n_extrinsics_priors; ++i)
-    if (p->extrinsics_prior_camera[i] < 0 || p->extrinsics_prior_camera[i] >= p->n_cameras)
-      bad("extrinsics prior camera out of range");
-  if (p->n_cameras && !p->extrinsics) bad("extrinsics == NULL");
-  if (p->n_imu) {
-    if (!p->imu_blocks || !p->imu_t0_ns || !p->imu_t1_ns || !p->imu_sample_begin || !p->imu_sample_t_ns ||
-        !p->imu_sample_gyr_acc)
-      bad("imu arrays missing");
-    for (int f = 0; f < p->n_imu; ++f) {
-      const int* b = &p->imu_blocks[4 * f];
-      if (b[0] < 0 || b[0] >= p->n_poses || b[2] < 0 || b[2] >= p->n_poses || b[1] < 0 ||
-          b[1] >= p->n_speed_biases || b[3] < 0 || b[3] >= p->n_speed_biases)
-        bad("imu block index out of range");
-      if (p->imu_sample_begin[f + 1] < p->imu_sample_begin[f]) bad("imu_sample_begin not monotone");
-    }
-  }
-  for (int i = 0; i < p->n_pose_priors; ++i)
-    if (p->pose_prior_block[i] < 0 || p->pose_prior_block[i] >= p->n_poses) bad("pose prior block out of range");
-  for (int i = 0; i < p->n_sb_priors; ++i)
-    if (p->sb_prior_block[i] < 0 || p->sb_prior_block[i] >= p->n_speed_biases) bad("sb prior block out of range");
-  if (p->n_relpose) {
-    if (!p->relpose_blocks || !p->relpose_delta_x || !p->relpose_sqrt_info || !p->relpose_lin_point)
-      bad("relative-pose arrays missing");
-    for (int i = 0; i < p->n_relpose; ++i) {
-      const int a = p->relpose_blocks[2 * i], b = p->relpose_blocks[2 * i + 1];
-      if (a < 0 || a >= p->n_poses || b < 0 || b >= p->n_poses) bad("relative-pose block out of range");
-      if (a == b) bad("relative-pose edge connects a pose to itself");
-      if (p->relpose_kind && p->relpose_kind[i] > 1) bad("unknown relative-pose kind");
-    }
-  }
-  if (p->n_host < 0) bad("negative count");
-  if (p->n_host) {
-    if (!p->host_dim || !p->host_param_kind || !p->host_param_index || !p->host_evaluate)
-      bad("host factor arrays / host_evaluate missing");
-    for (int h = 0; h < p->n_host; ++h) {
-      const std::string f = "host factor " + std::to_string(h) + ": ";
-      if (p->host_dim[h] < 1 || p->host_dim[h] > OKVISGPU_HOST_MAX_RESIDUALS) bad(f + "residual dimension out of range");
-      int np = 0, ns = 0, nb = 0;
-      for (int k = 0; k < 4; ++k) {
-        const int kind = p->host_param_kind[4 * h + k], idx = p->host_param_index[4 * h + k];
-        if (kind < 0) break;
-        ++nb;
-        if (kind == 0) {
-          if (idx < 0 || idx >= p->n_poses + p->n_cameras) bad(f + "pose-kind block out of range");
-          ++np;
-        } else if (kind == 1) {
-          if (idx < 0 || idx >= p->n_speed_biases) bad(f + "speed/bias block out of range");
-          ++ns;
-        } else {
-          throw UnsupportedError{"window " + std::to_string(w) + ": " + f +
-                                 "only pose-kind and speed/bias blocks can be host-evaluated"};
-        }
-        for (int j = 0; j < k; ++j)
-          if (p->host_param_kind[4 * h + j] == kind && p->host_param_index[4 * h + j] == idx)
-            bad(f + "parameter block repeated");
-        if (p->host_loss && !lossValid(p->host_loss[h])) bad(f + "unknown loss kind or non-positive loss scale");
-      }
-      for (int k = nb; k < 4; ++k)
-        if (p->host_param_kind[4 * h + k] >= 0) bad(f + "parameter blocks must be leading (kind -1 = none)");
-      if (nb == 0) bad(f + "no parameter block");
-      if (np > 2 || ns > 2)
-        throw UnsupportedError{"window " + std::to_string(w) + ": " + f +
-                               "more than 2 pose-kind or 2 speed/bias blocks"};
-    }
-  }
-}
-
-// Development: host-time split of analyse() (build with -DOKG_ANALYSE_TIMING; printed per build).
-#ifdef OKG_ANALYSE_TIMING
-double g_atime[16];
-std::chrono::steady_clock::time_point g_alast;
-#define ATIME(i)                                                                                    \
-  {                                                                                                 \
-    const auto now = std::chrono::steady_clock::now();                                             \
-    g_atime[i] += std::chrono::duration<double, std::milli>(now - g_alast).count();                 \
-    g_alast = now;                                                                                  \
-  }
-#else
-#define ATIME(i)
-#endif
-
-// Build the batch. `constOverride` carries okvisgpu_set_block_constant() edits.
-// ---- tile-level symbolic factorisation and the tile-parallel launch schedule -------------------
-// Fill of LLT inside the envelope, on the tile pattern nz (T x T, lower triangle).
-void symbolicFill(std::vector<uint8_t>& nz, int T) {
-  for (int k = 0; k < T; ++k)
-    for (int i = k + 1; i < T; ++i)
-      if (nz[(size_t)i * T + k])
-        for (int j = k + 1; j <= i; ++j)
-          if (nz[(size_t)j * T + k]) nz[(size_t)i * T + j] = 1;
-}
-// Launch schedule of the tile-parallel factorisation for a window's (filled) tile pattern: step k's
-// band updates (tiles (i, j), k < j <= i, L_ik and L_jk non-zero) run in launch L[k] >= 1; launch 0
-// factors the root tiles (those no update writes); any other tile is factored by the workgroup of
-// its last update, so step k starts one launch after that; no tile is written by two updates of
-// one launch. last[] holds each tile's last update launch (-1: none). For a block-banded pattern
-// this is launch k + 1 for step k (the pre-round-4 schedule); for a nested-dissection order the
-// independent parts share launches. Returns the number of launches.
-int cholSchedule(const std::vector<uint8_t>& nz, int T, std::vector<int>& L, std::vector<int>& last) {
-  L.assign(T, 0);
-  last.assign((size_t)T * T, -1);
-  int n = 1;
-  for (int k = 0; k < T; ++k) {
-    int lk = std::max(1, last[(size_t)k * T + k] + 1);
-    bool any = false;
-    for (int i = k + 1; i < T; ++i)
-      if (nz[(size_t)i * T + k])
-        for (int j = k + 1; j <= i; ++j)
-          if (nz[(size_t)j * T + k]) {
-            lk = std::max(lk, last[(size_t)i * T + j] + 1);
-            any = true;
-          }
-    L[k] = lk;
-    if (!any) continue;
-    for (int i = k + 1; i < T; ++i)
-      if (nz[(size_t)i * T + k])
-        for (int j = k + 1; j <= i; ++j)
-          if (nz[(size_t)j * T + k]) last[(size_t)i * T + j] = lk;
-    n = std::max(n, lk + 1);
-  }
-  return n;
-}
-inline int pad64(int x) { return (x + kTile - 1) / kTile * kTile; }
-// One level of nested dissection of a window's state slots (few windows: the latency of a solve is
-// the chain of the tile-parallel launches). Slots [0, a) (left) and [b, n) (right) share no factor
-// once the separator [a, b) is eliminated last: order left | right reversed | separator, left padded
-// to a tile boundary in S, so the two parts factor as independent chains that each reach the
-// separator only at their ends (the right part in natural order would touch it from its first
-// tile on, and every step would write the separator's tiles). dim[u] = f scalars of slot u,
-// reach[u] = largest slot coupled to u (landmarks seen from both, IMU links, edges, host factors).
-// The split is chosen on the launch count of the estimated tile pattern (interval couplings);
-// returns {-1, -1} unless it saves two launches or more with at most one tile more.
-std::pair<int, int> chooseNd(const std::vector<int>& dim, const std::vector<int>& reach) {
-  const int n = (int)dim.size();
-  auto estimate = [&](int a, int b, int& tiles) {
-    std::vector<int> order;  // (a = 0: the natural order)
-    for (int u = 0; u < (a > 0 ? a : n); ++u) order.push_back(u);
-    if (a > 0) {
-      for (int u = n - 1; u >= b; --u) order.push_back(u);
-      for (int u = a; u < b; ++u) order.push_back(u);
-    }
-    std::vector<int> off(n, 0);
-    int o = 0;
-    for (int t = 0; t < n; ++t) {
-      if (t == a && a > 0 && a < n) o = pad64(o);
-      off[order[t]] = o;
-      o += dim[order[t]];
-    }
-    const int T = std::max(1, pad64(o) / kTile);
-    tiles = T;
-    std::vector<uint8_t> nz((size_t)T * T, 0);
-    for (int i = 0; i < T; ++i) nz[(size_t)i * T + i] = 1;
-    for (int u = 0; u < n; ++u) {
-      if (!dim[u]) continue;
-      for (int v = u; v <= reach[u]; ++v) {
-        if (!dim[v]) continue;
-        for (int ti = off[u] / kTile; ti <= (off[u] + dim[u] - 1) / kTile; ++ti)
-          for (int tj = off[v] / kTile; tj <= (off[v] + dim[v] - 1) / kTile; ++tj)
-            nz[(size_t)std::max(ti, tj) * T + std::min(ti, tj)] = 1;
-      }
-    }
-    symbolicFill(nz, T);
-    std::vector<int> L, last;
-    return cholSchedule(nz, T, L, last);
-  };
-  int t0 = 0;
-  const int base = estimate(0, 0, t0);
-  std::vector<int> pm(n + 1, -1);
-  for (int u = 0; u < n; ++u) pm[u + 1] = std::max(pm[u], reach[u]);
-  int best = base, ba = -1, bb = -1;
-  const int stride = n > 64 ? n / 32 : 1;
-  for (int a = std::max(1, n > 64 ? n / 4 : 1); a < (n > 64 ? 3 * n / 4 : n - 1); a += stride) {
-    const int b = std::max(a, pm[a] + 1);
-    if (b >= n) continue;
-    int t = 0;
-    const int lv = estimate(a, b, t);
-    if (t <= t0 + 1 && lv < best) {
-      best = lv;
-      ba = a;
-      bb = b;
-    }
-  }
-  return best <= base - 2 ? std::make_pair(ba, bb) : std::make_pair(-1, -1);
-}
-
-void analyse(const std::vector<const okvisgpu_problem*>& probs,
-             const std::map<std::tuple<int, int, int>, int>& constOverride, HostBatch& B) {
-  B.seg_gbegin.push_back(0);
-  B.part_gbegin.push_back(0);
-  B.n_win = (int)probs.size();
-  B.probs = probs;
-  {  // capacity for the per-observation / per-landmark arrays of the whole batch (no regrowth)
-    size_t no = 0, nl = 0;
-    for (const okvisgpu_problem* p : probs) {
-      no += (size_t)std::max(0, p->n_observations);
-      nl += (size_t)std::max(0, p->n_landmarks);
-    }
-    for (auto* v : {&B.obs_pose, &B.obs_lm, &B.obs_cam, &B.obs_win, &B.obs_orig, &B.visit_pose, &B.visit_lm,
-                    &B.visit_obs_begin})
-      v->reserve(no + 1);
-    B.obs_flags.reserve(no);
-    B.obs_kp.reserve(2 * no);
-    B.obs_L.reserve(4 * no);
-    B.lm.reserve(4 * nl);
-    B.lm_perm.reserve(nl);
-    B.lm_visit_begin.reserve(nl + 1);
-    B.lm_win.reserve(nl);
-    B.lm_free.reserve(nl);
-  }
-  B.n_imu_total = 0;  // host factors are numbered after every IMU factor of the batch
-  for (const okvisgpu_problem* p : probs) B.n_imu_total += std::max(0, p->n_imu);
-  for (int w = 0; w < B.n_win; ++w) {
-    ATIME(0)
-    const okvisgpu_problem* p = probs[w];
-    validate(p, w);
-    const int pb = (int)B.pose_win.size(), sbb = (int)B.sb_win.size(), lb = (int)B.lm_win.size();
-    const int cb = (int)(B.cam.size() / kCamDoubles), ob = (int)B.obs_win.size(), ib = (int)B.imu_win.size();
-    const int ppb = (int)B.pp_win.size(), sbpb = (int)B.sbp_win.size(), rpb = (int)B.rp_win.size();
-    B.pose_base.push_back(pb); B.sb_base.push_back(sbb); B.lm_base.push_back(lb); B.cam_base.push_back(cb);
-    B.obs_base.push_back(ob); B.imu_base.push_back(ib); B.pp_base.push_back(ppb); B.sbp_base.push_back(sbpb);
-    B.rp_base.push_back(rpb);
-    auto isConst = [&](int kind, int idx, const uint8_t* flags) {
-      auto it = constOverride.find(std::make_tuple(w, kind, idx));
-      if (it != constOverride.end()) return it->second != 0;
-      return flags ? flags[idx] != 0 : false;
-    };
-    // pose-kind blocks of the window: the states' poses [0, np), then one extrinsics block per
-    // camera [np, np + ncam) (okvis: PoseParameterBlocks with the PoseManifold, ViGraph.cpp:330-336)
-    const int np = p->n_poses, ncam = p->n_cameras, npx = np + ncam;
-    std::vector<uint8_t> pc(npx), sc(p->n_speed_biases), lc(p->n_landmarks);
-    for (int i = 0; i < np; ++i) pc[i] = isConst(0, i, p->pose_constant);
-    for (int c = 0; c < ncam; ++c) {  // constant unless flagged variable (do_extrinsics: false)
-      auto it = constOverride.find(std::make_tuple(w, 3, c));
-      pc[np + c] = it != constOverride.end() ? it->second != 0
-                                             : (p->extrinsics_constant ? p->extrinsics_constant[c] != 0 : 1);
-    }
-    for (int i = 0; i < p->n_speed_biases; ++i) sc[i] = isConst(1, i, p->speed_bias_constant);
-    for (int i = 0; i < p->n_landmarks; ++i) lc[i] = isConst(2, i, p->landmark_constant);
-    // parameters
-    appendN(B.pose, p->poses, (size_t)7 * p->n_poses);
-    appendN(B.pose, p->extrinsics, (size_t)7 * ncam);
-    appendN(B.sb, p->speed_biases, (size_t)9 * p->n_speed_biases);
-    // internal landmark order: by first observing pose (then caller order), so that the visits of
-    // neighbouring keyframes are close in memory whatever order the caller numbers landmarks in
-    // (okvis numbers them by creation, which is nearly this order already)
-    std::vector<int> perm(p->n_landmarks), inv(p->n_landmarks);
-    {
-      std::vector<int> firstPose(p->n_landmarks, p->n_poses);
-      for (int o = 0; o < p->n_observations; ++o)
-        firstPose[p->obs_landmark[o]] = std::min(firstPose[p->obs_landmark[o]], p->obs_pose[o]);
-      std::iota(perm.begin(), perm.end(), 0);
-      std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return firstPose[a] < firstPose[b]; });
-      for (int k = 0; k < p->n_landmarks; ++k) inv[perm[k]] = k;
-    }
-    for (int k = 0; k < p->n_landmarks; ++k) {
-      appendN(B.lm, &p->landmarks[4 * (size_t)perm[k]], 4);
-      B.lm_perm.push_back(perm[k]);
-    }
-    for (int c = 0; c < p->n_cameras; ++c) {
-      const okvisgpu_camera& k = p->cameras[c];
-      const double cv[kCamDoubles] = {(double)k.distortion, k.fu, k.fv, k.cu, k.cv, k.dist[0], k.dist[1],
-                                      k.dist[2], k.dist[3], k.dist[4], k.dist[5], k.dist[6], k.dist[7]};
-      appendN(B.cam, cv, kCamDoubles);
-      appendN(B.extr, &p->extrinsics[7 * c], 7);
-      B.cam_pose.push_back(pb + np + c);
-    }
-    for (int i = 0; i < npx; ++i) B.pose_win.push_back(w);
-    for (int i = 0; i < p->n_speed_biases; ++i) B.sb_win.push_back(w);
-    for (int i = 0; i < p->n_landmarks; ++i) B.lm_win.push_back(w);
-    ATIME(1)
-    // active blocks: free and used by a residual block that is not entirely constant
-    std::vector<uint8_t> pa(npx, 0), sa(p->n_speed_biases, 0), la(p->n_landmarks, 0);
-    std::vector<uint8_t> ofix(p->n_observations), ifix(p->n_imu);
-    for (int o = 0; o < p->n_observations; ++o) {
-      const int ps = p->obs_pose[o], l = p->obs_landmark[o], xe = np + p->obs_camera[o];
-      ofix[o] = pc[ps] && lc[l] && pc[xe];
-      if (!pc[ps]) pa[ps] = 1;
-      if (!lc[l]) la[l] = 1;
-      if (!pc[xe]) pa[xe] = 1;
-    }
-    for (int f = 0; f < p->n_imu; ++f) {
-      const int* b = &p->imu_blocks[4 * f];
-      ifix[f] = pc[b[0]] && sc[b[1]] && pc[b[2]] && sc[b[3]];
-      if (!pc[b[0]]) pa[b[0]] = 1;
-      if (!sc[b[1]]) sa[b[1]] = 1;
-      if (!pc[b[2]]) pa[b[2]] = 1;
-      if (!sc[b[3]]) sa[b[3]] = 1;
-    }
-    // PoseError priors on pose-kind blocks: the states' (pose_prior_*) then the extrinsics'
-    // (extrinsics_prior_*, ViGraph.cpp:372-382), one prior list on the device
-    struct PPrior { int blk; const double* meas; const double* L; };
-    std::vector<PPrior> pps;
-    for (int i = 0; i < p->n_pose_priors; ++i)
-      pps.push_back(PPrior{p->pose_prior_block[i], &p->pose_prior_meas[7 * i], &p->pose_prior_sqrt_info[36 * i]});
-    for (int i = 0; i < p->n_extrinsics_priors; ++i)
-      pps.push_back(PPrior{np + p->extrinsics_prior_camera[i], &p->extrinsics_prior_meas[7 * i],
-                           &p->extrinsics_prior_sqrt_info[36 * i]});
-    for (const PPrior& q : pps)
-      if (!pc[q.blk]) pa[q.blk] = 1;
-    for (int i = 0; i < p->n_sb_priors; ++i)
-      if (!sc[p->sb_prior_block[i]]) sa[p->sb_prior_block[i]] = 1;
-    std::vector<uint8_t> rfix(p->n_relpose);
-    for (int i = 0; i < p->n_relpose; ++i) {
-      const int a = p->relpose_blocks[2 * i], b = p->relpose_blocks[2 * i + 1];
-      rfix[i] = pc[a] && pc[b];
-      if (!pc[a]) pa[a] = 1;
-      if (!pc[b]) pa[b] = 1;
-    }
-    // host-evaluated factors: IMU-layout slots (pose-kind blocks fill slots 0 then 2, speed/bias
-    // blocks 1 then 3, in the functor's order) and window-local block per slot (-1 unused)
-    const int hfBase = (int)B.hf.size();
-    std::vector<std::array<int, 4>> hslot(p->n_host);
-    std::vector<uint8_t> hfix(p->n_host);
-    for (int h = 0; h < p->n_host; ++h) {
-      HostBatch::HostFactor F{w, h, 0, p->host_dim[h], {-1, -1, -1, -1}, hostLoss(p, h)};
-      std::array<int, 4>& s = hslot[h];
-      s = {-1, -1, -1, -1};
-      int npk = 0, nsb = 0;
-      bool allConst = true;
-      for (int k = 0; k < 4 && p->host_param_kind[4 * h + k] >= 0; ++k) {
-        const int kind = p->host_param_kind[4 * h + k], idx = p->host_param_index[4 * h + k];
-        const int q = kind == 0 ? 2 * npk++ : 1 + 2 * nsb++;
-        F.slot[k] = (int8_t)q;
-        F.np = k + 1;
-        s[q] = idx;
-        const bool c = kind == 0 ? pc[idx] != 0 : sc[idx] != 0;
-        allConst = allConst && c;
-        if (!c) (kind == 0 ? pa[idx] : sa[idx]) = 1;
-      }
-      hfix[h] = allConst;
-      B.hf.push_back(F);
-    }
-    // f-blocks in the reduced ordering: pose i, then speed/bias i, state slot by slot; for the
-    // tile-parallel schedule (few windows) possibly in a nested-dissection order of the slots
-    std::vector<int> posef(npx, -1), sbf(p->n_speed_biases, -1), poseFb(npx, -1), sbFb(p->n_speed_biases, -1);
-    int fo = 0;
-    const int nmax = std::max(p->n_poses, p->n_speed_biases);
-    const int fbBase = (int)B.fb_win.size();
-    std::vector<int> slotOrder(nmax);
-    std::iota(slotOrder.begin(), slotOrder.end(), 0);
-    int ndLeft = 0, ndSep = 0;  // slots of the left part (0: natural order); order index of the separator
-    const bool extFree = std::any_of(pa.begin() + np, pa.end(), [](uint8_t a) { return a != 0; });
-    if (B.nd && !extFree && nmax >= 8) {  // (variable extrinsics couple every state: no split)
-      std::vector<int> dim(nmax, 0), reach(nmax);
-      for (int i = 0; i < nmax; ++i) {
-        dim[i] = (i < p->n_poses && pa[i] ? 6 : 0) + (i < p->n_speed_biases && sa[i] ? 9 : 0);
-        reach[i] = i;
-      }
-      auto couple = [&](int lo, int hi) {
-        if (lo >= 0 && hi > lo) reach[lo] = std::max(reach[lo], hi);
-      };
-      {  // landmarks: the free poses observing a free landmark are coupled by its elimination
-        std::vector<int> lo(p->n_landmarks, INT_MAX), hi(p->n_landmarks, -1);
-        for (int o = 0; o < p->n_observations; ++o) {
-          const int l = p->obs_landmark[o], ps = p->obs_pose[o];
-          if (!la[l] || !pa[ps]) continue;
-          lo[l] = std::min(lo[l], ps);
-          hi[l] = std::max(hi[l], ps);
-        }
-        for (int l = 0; l < p->n_landmarks; ++l)
-          if (hi[l] >= 0) couple(lo[l], hi[l]);
-      }
-      auto coupleSet = [&](std::initializer_list<int> slots) {
-        int lo = INT_MAX, hi = -1;
-        for (int u : slots)
-          if (u >= 0) { lo = std::min(lo, u); hi = std::max(hi, u); }
-        if (hi >= 0) couple(lo, hi);
-      };
-      for (int f = 0; f < p->n_imu; ++f) {
-        const int* b = &p->imu_blocks[4 * f];
-        coupleSet({pa[b[0]] ? b[0] : -1, sa[b[1]] ? b[1] : -1, pa[b[2]] ? b[2] : -1, sa[b[3]] ? b[3] : -1});
-      }
-      for (int i = 0; i < p->n_relpose; ++i) {
-        const int a = p->relpose_blocks[2 * i], b = p->relpose_blocks[2 * i + 1];
-        coupleSet({a < np && pa[a] ? a : -1, b < np && pa[b] ? b : -1});
-      }
-      for (int h = 0; h < p->n_host; ++h) {
-        int lo = INT_MAX, hi = -1;
-        for (int k = 0; k < 4 && p->host_param_kind[4 * h + k] >= 0; ++k) {
-          const int kind = p->host_param_kind[4 * h + k], idx = p->host_param_index[4 * h + k];
-          const bool act = kind == 0 ? (idx < np && pa[idx]) : sa[idx] != 0;
-          if (act) { lo = std::min(lo, idx); hi = std::max(hi, idx); }
-        }
-        if (hi >= 0) couple(lo, hi);
-      }
-      const auto ab = chooseNd(dim, reach);
-      if (ab.first > 0) {
-        slotOrder.clear();
-        for (int u = 0; u < ab.first; ++u) slotOrder.push_back(u);
-        for (int u = nmax - 1; u >= ab.second; --u) slotOrder.push_back(u);
-        for (int u = ab.first; u < ab.second; ++u) slotOrder.push_back(u);
-        ndLeft = ab.first;
-        ndSep = ab.first + (nmax - ab.second);
-      }
-    }
-    // (nested dissection: the left part ends on a tile boundary; the gap rows between are identity
-    // rows of S with zero rhs, so the f-vector and S share one index)
-    int gapAt = 0, gap = 0, rightAt = 0, sepAt = 0;
-    for (int t = 0; t < nmax; ++t) {
-      const int i = slotOrder[t];
-      if (ndLeft && t == ndLeft) {
-        gapAt = fo;
-        fo = pad64(fo);
-        gap = fo - gapAt;
-        rightAt = fo;
-      }
-      if (ndLeft && t == ndSep) sepAt = fo;
-      if (i < p->n_poses && pa[i]) {
-        posef[i] = fo;
-        poseFb[i] = (int)B.fb_win.size();
-        B.fb_win.push_back(w); B.fb_kind.push_back(0); B.fb_index.push_back(pb + i); B.fb_off.push_back(fo);
-        fo += 6;
-      }
-      if (i < p->n_speed_biases && sa[i]) {
-        sbf[i] = fo;
-        sbFb[i] = (int)B.fb_win.size();
-        B.fb_win.push_back(w); B.fb_kind.push_back(1); B.fb_index.push_back(sbb + i); B.fb_off.push_back(fo);
-        fo += 9;
-      }
-    }
-    // variable extrinsics after all states: S keeps the states' band plus a dense border
-    for (int c = 0; c < ncam; ++c) {
-      const int i = np + c;
-      if (!pa[i]) continue;
-      posef[i] = fo;
-      poseFb[i] = (int)B.fb_win.size();
-      B.fb_win.push_back(w); B.fb_kind.push_back(0); B.fb_index.push_back(pb + i); B.fb_off.push_back(fo);
-      fo += 6;
-    }
-    B.win_ext_free.push_back(fo > 0 && extFree);
-    B.win_sgap.push_back(gap ? gapAt : 0);
-    B.win_sgap.push_back(gap);
-    // natural order of the f entries (pose i, speed/bias i slot by slot, then extrinsics: the order
-    // of okvisgpu_linearize_reduce's export and of the oracle)
-    {
-      std::vector<int32_t> nat(fo, -1);
-      int no = 0;
-      auto put = [&](int f, int n) {
-        for (int c = 0; c < n; ++c) nat[f + c] = no++;
-      };
-      for (int i = 0; i < nmax; ++i) {
-        if (i < p->n_poses && posef[i] >= 0) put(posef[i], 6);
-        if (i < p->n_speed_biases && sbf[i] >= 0) put(sbf[i], 9);
-      }
-      for (int c = 0; c < ncam; ++c)
-        if (posef[np + c] >= 0) put(posef[np + c], 6);
-      B.f_nat.insert(B.f_nat.end(), nat.begin(), nat.end());
-      B.win_fnat.push_back(no);
-    }
-    for (int i = 0; i < npx; ++i) { B.pose_f.push_back(posef[i]); B.pose_active.push_back(pa[i]); }
-    for (int i = 0; i < p->n_speed_biases; ++i) { B.sb_f.push_back(sbf[i]); B.sb_active.push_back(sa[i]); }
-    std::vector<uint8_t> laNew(p->n_landmarks);
-    for (int k = 0; k < p->n_landmarks; ++k) laNew[k] = la[perm[k]];
-    for (int k = 0; k < p->n_landmarks; ++k) B.lm_free.push_back(laNew[k]);
-    const int fpad = pad64(fo);  // S dimension (leading dimension of the window's S)
-    B.win_foff.push_back(B.f_total);
-    B.win_fdim.push_back(fo);
-    B.win_fpad.push_back(fpad);
-    B.win_soff.push_back(B.s_total);
-    B.win_linvoff.push_back(B.linv_total);
-    B.win_fwdoff.push_back(B.fwd_total);
-    B.fwd_total += fpad;
-    B.f_total += fo;
-    B.s_total += (int64_t)fpad * fpad;
-    B.linv_total += (int64_t)(fpad / kTile) * kTile * kTile;
-    B.max_fpad = std::max(B.max_fpad, fpad);
-
-    ATIME(2)
-    // observations sorted by (internal landmark, pose, camera, original index)
-    // (counting sort by landmark, then insertion sort of each landmark's few observations: the
-    // order of a stable sort on that key, in linear time)
-    std::vector<int> order(p->n_observations);
-    {
-      std::vector<int> start(p->n_landmarks + 1, 0);
-      for (int o = 0; o < p->n_observations; ++o) ++start[inv[p->obs_landmark[o]] + 1];
-      for (int l = 0; l < p->n_landmarks; ++l) start[l + 1] += start[l];
-      std::vector<int> fill(start.begin(), start.end() - 1);
-      for (int o = 0; o < p->n_observations; ++o) order[fill[inv[p->obs_landmark[o]]]++] = o;
-      auto before = [&](int a, int b) {
-        if (p->obs_pose[a] != p->obs_pose[b]) return p->obs_pose[a] < p->obs_pose[b];
-        if (p->obs_camera[a] != p->obs_camera[b]) return p->obs_camera[a] < p->obs_camera[b];
-        return a < b;
-      };
-      for (int l = 0; l < p->n_landmarks; ++l)
-        for (int i = start[l] + 1; i < start[l + 1]; ++i) {
-          const int x = order[i];
-          int j = i - 1;
-          for (; j >= start[l] && before(x, order[j]); --j) order[j + 1] = order[j];
-          order[j + 1] = x;
-        }
-    }
-    ATIME(3)
-    // visits and landmark -> visit ranges
-    const int vBase = (int)B.visit_pose.size();
-    std::vector<int> lmVisitBegin(p->n_landmarks + 1, 0);
-    std::vector<std::vector<int>> visitsAtPose(p->n_poses);
-    {
-      int prevL = -1, prevP = -1;
-      std::vector<int> vcount(p->n_landmarks, 0);
-      // per-observation arrays written in place (sized once; push_back per element dominated)
-      const size_t nob = (size_t)p->n_observations;
-      for (auto* v : {&B.obs_pose, &B.obs_lm, &B.obs_cam, &B.obs_win, &B.obs_orig}) v->resize(ob + nob);
-      B.obs_flags.resize(ob + nob);
-      B.obs_kp.resize(2 * (ob + nob));
-      B.obs_L.resize(4 * (ob + nob));
-      int32_t *oPose = B.obs_pose.data() + ob, *oLm = B.obs_lm.data() + ob, *oCam = B.obs_cam.data() + ob,
-              *oWin = B.obs_win.data() + ob, *oOrig = B.obs_orig.data() + ob;
-      uint8_t* oFl = B.obs_flags.data() + ob;
-      double *oKp = B.obs_kp.data() + 2 * (size_t)ob, *oL = B.obs_L.data() + 4 * (size_t)ob;
-      for (int k = 0; k < p->n_observations; ++k) {
-        const int o = order[k];
-        const int l = inv[p->obs_landmark[o]], ps = p->obs_pose[o], cam = p->obs_camera[o];
-        oPose[k] = pb + ps;
-        oLm[k] = lb + l;
-        oCam[k] = cb + cam;
-        oWin[k] = w;
-        oOrig[k] = o;
-        uint8_t fl = 0;
-        if (p->obs_cauchy ? p->obs_cauchy[o] != 0 : true) fl |= 1;
-        if (ofix[o]) fl |= 2;
-        if (posef[np + cam] >= 0) fl |= 4;  // variable extrinsics
-        oFl[k] = fl;
-        oKp[2 * k] = p->obs_keypoint[2 * o];
-        oKp[2 * k + 1] = p->obs_keypoint[2 * o + 1];
-        for (int i = 0; i < 4; ++i) oL[4 * k + i] = p->obs_sqrt_info[4 * o + i];
-        if (l != prevL || ps != prevP) {
-          B.visit_pose.push_back(pb + ps);
-          B.visit_lm.push_back(lb + l);
-          B.visit_obs_begin.push_back(ob + k);
-          visitsAtPose[ps].push_back((int)B.visit_pose.size() - 1);
-          vcount[l]++;
-          prevL = l;
-          prevP = ps;
-        }
-      }
-      int acc = vBase;
-      for (int l = 0; l < p->n_landmarks; ++l) {
-        lmVisitBegin[l] = acc;
-        acc += vcount[l];
-      }
-      lmVisitBegin[p->n_landmarks] = acc;
-      for (int l = 0; l < p->n_landmarks; ++l) B.lm_visit_begin.push_back(lmVisitBegin[l]);
-    }
-    ATIME(4)
-    // extrinsic visits: per landmark and variable camera, the landmark's (non-fixed) observations
-    // through that camera (the extrinsics block is the third parameter block of their
-    // ReprojectionErrors); global indices, in landmark order like the visits
-    std::vector<int> lmXBegin(p->n_landmarks + 1, (int)B.xvisit_pose.size());
-    {
-      std::vector<int> freeCams;
-      for (int c = 0; c < ncam; ++c)
-        if (posef[np + c] >= 0) freeCams.push_back(c);
-      int k = 0;
-      for (int l = 0; l < p->n_landmarks; ++l) {
-        lmXBegin[l] = (int)B.xvisit_pose.size();
-        const int k0 = k;
-        while (k < p->n_observations && inv[p->obs_landmark[order[k]]] == l) ++k;
-        for (int c : freeCams) {
-          std::vector<int32_t> obs;
-          for (int j = k0; j < k; ++j)
-            if (p->obs_camera[order[j]] == c && !ofix[order[j]]) obs.push_back(ob + j);
-          if (obs.empty()) continue;
-          B.xvisit_pose.push_back(pb + np + c);
-          B.xvisit_lm.push_back(lb + l);
-          B.xvisit_obs_begin.push_back((int32_t)B.xvisit_obs.size());
-          B.xvisit_obs.insert(B.xvisit_obs.end(), obs.begin(), obs.end());
-          B.xvisit_slot.push_back(-1);
-        }
-      }
-      lmXBegin[p->n_landmarks] = (int)B.xvisit_pose.size();
-    }
-    ATIME(5)
-    // landmark groups of k_lm_visit (consecutive whole landmarks of this window, <= kLmGroupVisits
-    // visits and <= kLmGroupMax landmarks; one workgroup, one thread per visit) and their visit
-    // segments: the visits of a group that belong to one free pose, pre-summed by k_lm_visit into
-    // one H | g and one U z record (ascending pose; members in visit order)
-    std::vector<std::vector<int>> segsAtPose(npx);
-    std::vector<std::pair<int, int>> partKeys;  // f-block pair of each partial block of this window
-    const int partBase = (int)B.part_cbegin.size();
-    {
-      // each visit of a free pose gets the slot of its position in the group's (pose, visit)
-      // order, so a segment is a contiguous slot range [seg_range.x, seg_range.y)
-      // A group's threads: its pose visits first (thread t = v - gv0), then its extrinsic visits
-      // (thread t = nvg + xv - gx0).
-      std::vector<std::pair<int, int>> mem, gitems, gprod;  // scratch reused by every group
-      std::vector<int> glocal, gcount, gfill, fbLocal(std::max(1, (int)B.fb_off.size()), -1);
-      std::vector<int32_t> gsorted;
-      auto closeGroup = [&](int gl0, int gl1) {
-        const int gv0 = lmVisitBegin[gl0], gv1 = lmVisitBegin[gl1], nvg = gv1 - gv0;
-        const int gx0 = lmXBegin[gl0], gx1 = lmXBegin[gl1];
-        // members (v >= 0 visit, -1 - xv extrinsic visit) grouped by pose-kind block, ascending,
-        // each block's members in visit order
-        mem.clear();
-        for (int v = gv0; v < gv1; ++v) {
-          const int ps = B.visit_pose[v] - pb;
-          if (posef[ps] >= 0) mem.push_back({ps, v});
-          else B.visit_slot[v] = -1;
-        }
-        for (int xv = gx0; xv < gx1; ++xv) mem.push_back({B.xvisit_pose[xv] - pb, -1 - xv});
-        std::stable_sort(mem.begin(), mem.end(),
-                         [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
-        int slot = 0;
-        for (size_t m = 0; m < mem.size();) {
-          const int ps = mem[m].first;
-          segsAtPose[ps].push_back((int)B.seg_pose.size());
-          B.seg_pose.push_back(pb + ps);
-          B.seg_range.push_back(slot);
-          for (; m < mem.size() && mem[m].first == ps; ++m) {
-            const int v = mem[m].second;
-            if (v >= 0) B.visit_slot[v] = slot++;
-            else B.xvisit_slot[-1 - v] = slot++;
-          }
-          B.seg_range.push_back(slot);
-        }
-        // partial Schur blocks (k_lm_visit): per f-block pair (row >= col by f offset) the products
-        // Z_a Z_b^T of the group's free landmarks; contributions packed as (a | b << 16), thread
-        // offsets within the group
-        // products keyed by f-block pair, in (row f-block, col f-block) order, each key's products
-        // in generation order: the group's f-blocks get dense local indices in ascending order and
-        // the products are counting-sorted by (local row, local col)
-        std::vector<std::pair<int, int>>& items = gitems;  // (thread, f-block) of one landmark's free visits
-        glocal.clear();
-        for (int v = gv0; v < gv1; ++v)
-          if (laNew[B.visit_lm[v] - lb] && poseFb[B.visit_pose[v] - pb] >= 0) glocal.push_back(poseFb[B.visit_pose[v] - pb]);
-        for (int xv = gx0; xv < gx1; ++xv)
-          if (laNew[B.xvisit_lm[xv] - lb]) glocal.push_back(poseFb[B.xvisit_pose[xv] - pb]);
-        std::sort(glocal.begin(), glocal.end());
-        glocal.erase(std::unique(glocal.begin(), glocal.end()), glocal.end());
-        const int nloc = (int)glocal.size();
-        for (int i = 0; i < nloc; ++i) fbLocal[glocal[i]] = i;
-        gprod.clear();
-        for (int l = gl0; l < gl1; ++l) {
-          if (!laNew[l]) continue;
-          items.clear();
-          for (int va = lmVisitBegin[l]; va < lmVisitBegin[l + 1]; ++va) {
-            const int fa = poseFb[B.visit_pose[va] - pb];
-            if (fa >= 0) items.push_back({va - gv0, fa});
-          }
-          for (int xv = lmXBegin[l]; xv < lmXBegin[l + 1]; ++xv)
-            items.push_back({nvg + xv - gx0, poseFb[B.xvisit_pose[xv] - pb]});
-          for (const auto& a : items)
-            for (const auto& b : items) {
-              if (B.fb_off[a.second] < B.fb_off[b.second]) continue;
-              gprod.push_back({fbLocal[a.second] * nloc + fbLocal[b.second], a.first | (b.first << 16)});
-            }
-        }
-        gcount.assign((size_t)nloc * nloc + 1, 0);
-        for (const auto& x : gprod) ++gcount[x.first + 1];
-        for (int k = 0; k < nloc * nloc; ++k) gcount[k + 1] += gcount[k];
-        gsorted.resize(gprod.size());
-        gfill.assign(gcount.begin(), gcount.end() - 1);
-        for (const auto& x : gprod) gsorted[gfill[x.first]++] = x.second;
-        // long blocks are split into chunks of <= kPartChunk products (separate records, summed
-        // in order by k_assemble_pp) so that no k_lm_visit thread serialises a whole block
-        constexpr int kPartChunk = 24;  // measured: 6 / 12 / 24 / unsplit on 2048 S50 windows
-        for (int key = 0; key < nloc * nloc; ++key) {
-          const int k0 = gcount[key], k1 = gcount[key + 1];
-          for (int c0 = k0; c0 < k1; c0 += kPartChunk) {
-            const int c1 = std::min(k1, c0 + kPartChunk);
-            partKeys.push_back({glocal[key / nloc], glocal[key % nloc]});
-            B.part_cbegin.push_back((int)B.part_contrib.size());
-            B.part_contrib.insert(B.part_contrib.end(), gsorted.begin() + c0, gsorted.begin() + c1);
-          }
-        }
-        B.lmg_begin.push_back(lb + gl0);
-        B.lmg_xbegin.push_back(gx0);
-        B.seg_gbegin.push_back((int)B.seg_pose.size());
-        B.part_gbegin.push_back((int)B.part_cbegin.size());
-      };
-      // landmark-pair products a group stages in LDS (kLmPartStage) bound the group as well; only
-      // visits of free poses form products. A landmark with more products than the stage holds
-      // (>= 64 free observing poses, e.g. a long track in a full graph) gets a group of its own
-      // whose products k_lm_visit streams from HBM instead.
-      auto pairCount = [&](int l) {
-        if (!laNew[l]) return 0;
-        int nf = lmXBegin[l + 1] - lmXBegin[l];
-        for (int v = lmVisitBegin[l]; v < lmVisitBegin[l + 1]; ++v) nf += posef[B.visit_pose[v] - pb] >= 0;
-        return nf * (nf + 1) / 2;
-      };
-      int gpc = 0;
-      B.visit_slot.resize(B.visit_pose.size(), -1);
-      int g0 = 0, gl = 0;
-      for (int l = 0; l < p->n_landmarks; ++l) {
-        const int nv = lmVisitBegin[l + 1] - lmVisitBegin[l] + lmXBegin[l + 1] - lmXBegin[l];
-        if (nv > kLmGroupVisits)
-          throw ArgError{"landmark with more than " + std::to_string(kLmGroupVisits) + " observing poses"};
-        const int gv = lmVisitBegin[l] - lmVisitBegin[g0] + lmXBegin[l] - lmXBegin[g0];
-        const int pcl = pairCount(l);
-        if (l > g0 && (gv + nv > B.lmg_visits || gl == B.lmg_lms || gpc + pcl > kLmPartStage)) {
-          closeGroup(g0, l);
-          g0 = l;
-          gl = 0;
-          gpc = 0;
-        }
-        ++gl;
-        gpc += pcl;
-      }
-      if (p->n_landmarks > 0) closeGroup(g0, p->n_landmarks);
-    }
-    ATIME(6)
-    // imu
-    const int sBase = (int)B.imu_ts.size();
-    for (int f = 0; f < p->n_imu; ++f) {
-      const int* b = &p->imu_blocks[4 * f];
-      const int32_t gb[4] = {pb + b[0], sbb + b[1], pb + b[2], sbb + b[3]};
-      appendN(B.imu_blocks, gb, 4);
-      B.imu_win.push_back(w);
-      B.imu_flags.push_back(ifix[f] ? 2 : 0);
-      B.imu_t0.push_back(p->imu_t0_ns[f]);
-      B.imu_t1.push_back(p->imu_t1_ns[f]);
-      B.imu_sbegin.push_back(sBase + p->imu_sample_begin[f] - p->imu_sample_begin[0]);
-    }
-    if (p->n_imu) {
-      const int s0 = p->imu_sample_begin[0], s1 = p->imu_sample_begin[p->n_imu];
-      appendN(B.imu_ts, &p->imu_sample_t_ns[s0], (size_t)(s1 - s0));
-      appendN(B.imu_ga, &p->imu_sample_gyr_acc[6 * (size_t)s0], (size_t)6 * (s1 - s0));
-    }
-    {
-      const okvisgpu_imu_params& ip = p->imu_params;
-      const double par[7] = {ip.a_max, ip.g_max, ip.sigma_g_c, ip.sigma_a_c, ip.sigma_gw_c, ip.sigma_aw_c, ip.g};
-      appendN(B.imu_par, par, 7);
-    }
-    for (int f = 0; f < p->n_imu; ++f) {
-      if (p->imu_state) appendN(B.imu_state, &p->imu_state[(size_t)f * OKVISGPU_IMU_STATE_DOUBLES], OKVISGPU_IMU_STATE_DOUBLES);
-      else B.imu_state.insert(B.imu_state.end(), OKVISGPU_IMU_STATE_DOUBLES, 0.0);
-    }
-    // host-evaluated factors (global pose-kind / speed-bias indices per slot)
-    const int hgBase = B.n_imu_total + hfBase;  // global factor index of this window's first
-    for (int h = 0; h < p->n_host; ++h) {
-      const std::array<int, 4>& s = hslot[h];
-      const int32_t gb[4] = {s[0] < 0 ? -1 : pb + s[0], s[1] < 0 ? -1 : sbb + s[1], s[2] < 0 ? -1 : pb + s[2],
-                             s[3] < 0 ? -1 : sbb + s[3]};
-      appendN(B.host_blocks, gb, 4);
-      B.host_win.push_back(w);
-      B.host_flags.push_back(hfix[h] ? 2 : 0);
-    }
-    {
-      const int r_host[2] = {hgBase, hgBase + p->n_host};
-      appendN(B.win_host_range, r_host, 2);
-    }
-    // priors
-    for (const PPrior& q : pps) {
-      B.pp_block.push_back(pb + q.blk);
-      B.pp_win.push_back(w);
-      appendN(B.pp_meas, q.meas, 7);
-      appendN(B.pp_L, q.L, 36);
-    }
-    for (int i = 0; i < p->n_sb_priors; ++i) {
-      B.sbp_block.push_back(sbb + p->sb_prior_block[i]);
-      B.sbp_win.push_back(w);
-      appendN(B.sbp_meas, &p->sb_prior_meas[9 * i], 9);
-      appendN(B.sbp_L, &p->sb_prior_sqrt_info[81 * i], 81);
-    }
-    for (int i = 0; i < p->n_relpose; ++i) {
-      B.rp_blocks.push_back(pb + p->relpose_blocks[2 * i]);
-      B.rp_blocks.push_back(pb + p->relpose_blocks[2 * i + 1]);
-      B.rp_win.push_back(w);
-      B.rp_flags.push_back(rfix[i] ? 2 : 0);
-      B.rp_kind.push_back(p->relpose_kind ? p->relpose_kind[i] : 0);
-      appendN(B.rp_dx, &p->relpose_delta_x[6 * i], 6);
-      appendN(B.rp_J, &p->relpose_sqrt_info[36 * i], 36);
-      appendN(B.rp_lp, &p->relpose_lin_point[7 * i], 7);
-    }
-    // ranges
-    const int r_pose[2] = {pb, pb + npx}, r_sb[2] = {sbb, sbb + p->n_speed_biases},
-              r_lm[2] = {lb, lb + p->n_landmarks}, r_obs[2] = {ob, ob + p->n_observations},
-              r_imu[2] = {ib, ib + p->n_imu}, r_pp[2] = {ppb, ppb + (int)pps.size()},
-              r_sbp[2] = {sbpb, sbpb + p->n_sb_priors}, r_rp[2] = {rpb, rpb + p->n_relpose};
-    appendN(B.win_pose_range, r_pose, 2); appendN(B.win_sb_range, r_sb, 2); appendN(B.win_lm_range, r_lm, 2);
-    appendN(B.win_obs_range, r_obs, 2); appendN(B.win_imu_range, r_imu, 2); appendN(B.win_pp_range, r_pp, 2);
-    appendN(B.win_sbp_range, r_sbp, 2);
-    appendN(B.win_rp_range, r_rp, 2);
-
-    ATIME(7)
-    // ---- f-block gradient / diagonal contribution lists
-    const int nFb = (int)B.fb_win.size() - fbBase;
-    std::vector<std::vector<Contrib>> fbc(nFb);
-    for (int i = 0; i < npx; ++i) {
-      if (poseFb[i] < 0) continue;
-      for (int sg : segsAtPose[i]) fbc[poseFb[i] - fbBase].push_back(Contrib{C_VISIT, sg, 0, 0});
-    }
-    const int imuCol[4] = {0, 6, 15, 21};
-    for (int f = 0; f < p->n_imu; ++f) {
-      if (ifix[f]) continue;
-      const int* b = &p->imu_blocks[4 * f];
-      const int fbs[4] = {poseFb[b[0]], sbFb[b[1]], poseFb[b[2]], sbFb[b[3]]};
-      for (int q = 0; q < 4; ++q)
-        if (fbs[q] >= 0) fbc[fbs[q] - fbBase].push_back(Contrib{C_IMU, ib + f, imuCol[q], imuCol[q]});
-    }
-    // host factors' slot f-blocks (-1: unused slot or constant block)
-    auto hostFbs = [&](int h, int* fbs) {
-      const std::array<int, 4>& s = hslot[h];
-      for (int q = 0; q < 4; ++q) fbs[q] = s[q] < 0 ? -1 : (q & 1) ? sbFb[s[q]] : poseFb[s[q]];
-    };
-    for (int h = 0; h < p->n_host; ++h) {
-      if (hfix[h]) continue;
-      int fbs[4];
-      hostFbs(h, fbs);
-      for (int q = 0; q < 4; ++q)
-        if (fbs[q] >= 0) fbc[fbs[q] - fbBase].push_back(Contrib{C_IMU, hgBase + h, imuCol[q], imuCol[q]});
-    }
-    for (size_t i = 0; i < pps.size(); ++i) {
-      const int fb = poseFb[pps[i].blk];
-      if (fb >= 0) fbc[fb - fbBase].push_back(Contrib{C_PPRIOR, ppb + (int)i, 0, 0});
-    }
-    for (int i = 0; i < p->n_sb_priors; ++i) {
-      const int fb = sbFb[p->sb_prior_block[i]];
-      if (fb >= 0) fbc[fb - fbBase].push_back(Contrib{C_SBPRIOR, sbpb + i, 0, 0});
-    }
-    for (int i = 0; i < p->n_relpose; ++i) {
-      if (rfix[i]) continue;
-      for (int q = 0; q < 2; ++q) {
-        const int fb = poseFb[p->relpose_blocks[2 * i + q]];
-        if (fb >= 0) fbc[fb - fbBase].push_back(Contrib{C_RELPOSE, rpb + i, 6 * q, 6 * q});
-      }
-    }
-    for (int k = 0; k < nFb; ++k) {
-      B.fb_cbegin.push_back((int)B.fb_contrib.size());
-      B.fb_contrib.insert(B.fb_contrib.end(), fbc[k].begin(), fbc[k].end());
-    }
-    ATIME(8)
-    // ---- block pairs (fi >= fj by reduced offset) and their contribution lists
-    std::map<std::pair<int, int>, std::vector<Contrib>> pairs;
-    auto key = [&](int fa, int fb2) {  // row = larger offset
-      return B.fb_off[fa] >= B.fb_off[fb2] ? std::make_pair(fa, fb2) : std::make_pair(fb2, fa);
-    };
-    for (int i = 0; i < npx; ++i) {
-      if (poseFb[i] < 0) continue;
-      auto& lst = pairs[std::make_pair(poseFb[i], poseFb[i])];
-      for (int sg : segsAtPose[i]) lst.push_back(Contrib{C_VISIT, sg, 0, 0});
-    }
-    for (size_t k = 0; k < partKeys.size(); ++k)  // partial Schur blocks, group order
-      pairs[partKeys[k]].push_back(Contrib{C_PAIR, partBase + (int)k, 0, 0});
-    for (int f = 0; f < p->n_imu; ++f) {
-      if (ifix[f]) continue;
-      const int* b = &p->imu_blocks[4 * f];
-      const int fbs[4] = {poseFb[b[0]], sbFb[b[1]], poseFb[b[2]], sbFb[b[3]]};
-      for (int u = 0; u < 4; ++u)
-        for (int v = 0; v < 4; ++v) {
-          if (fbs[u] < 0 || fbs[v] < 0) continue;
-          if (B.fb_off[fbs[u]] < B.fb_off[fbs[v]]) continue;
-          pairs[key(fbs[u], fbs[v])].push_back(Contrib{C_IMU, ib + f, imuCol[u], imuCol[v]});
-        }
-    }
-    for (int h = 0; h < p->n_host; ++h) {
-      if (hfix[h]) continue;
-      int fbs[4];
-      hostFbs(h, fbs);
-      for (int u = 0; u < 4; ++u)
-        for (int v = 0; v < 4; ++v) {
-          if (fbs[u] < 0 || fbs[v] < 0) continue;
-          if (B.fb_off[fbs[u]] < B.fb_off[fbs[v]]) continue;
-          pairs[key(fbs[u], fbs[v])].push_back(Contrib{C_IMU, hgBase + h, imuCol[u], imuCol[v]});
-        }
-    }
-    for (size_t i = 0; i < pps.size(); ++i) {
-      const int fb = poseFb[pps[i].blk];
-      if (fb >= 0) pairs[std::make_pair(fb, fb)].push_back(Contrib{C_PPRIOR, ppb + (int)i, 0, 0});
-    }
-    // pose-extrinsics cross blocks: sum over the observations of a free state pose through a
-    // variable camera of J_e^T J_p (k_pose_extr); row = the extrinsics block (after all states)
-    for (int ps = 0; ps < np; ++ps) {
-      if (poseFb[ps] < 0) continue;
-      for (int c = 0; c < ncam; ++c) {
-        if (poseFb[np + c] < 0) continue;
-        std::vector<int32_t> obs;
-        for (int k = 0; k < p->n_observations; ++k) {
-          const int o = order[k];
-          if (p->obs_pose[o] == ps && p->obs_camera[o] == c && !ofix[o]) obs.push_back(ob + k);
-        }
-        if (obs.empty()) continue;
-        pairs[key(poseFb[np + c], poseFb[ps])].push_back(Contrib{C_PEXT, (int)B.pe_pose.size(), 0, 0});
-        B.pe_pose.push_back(pb + ps);
-        B.pe_ext.push_back(pb + np + c);
-        B.pe_obs_begin.push_back((int32_t)B.pe_obs.size());
-        B.pe_obs.insert(B.pe_obs.end(), obs.begin(), obs.end());
-      }
-    }
-    for (int i = 0; i < p->n_sb_priors; ++i) {
-      const int fb = sbFb[p->sb_prior_block[i]];
-      if (fb >= 0) pairs[std::make_pair(fb, fb)].push_back(Contrib{C_SBPRIOR, sbpb + i, 0, 0});
-    }
-    for (int i = 0; i < p->n_relpose; ++i) {
-      if (rfix[i]) continue;
-      const int fbs[2] = {poseFb[p->relpose_blocks[2 * i]], poseFb[p->relpose_blocks[2 * i + 1]]};
-      for (int u = 0; u < 2; ++u)
-        for (int v = 0; v < 2; ++v) {
-          if (fbs[u] < 0 || fbs[v] < 0) continue;
-          if (B.fb_off[fbs[u]] < B.fb_off[fbs[v]]) continue;
-          pairs[key(fbs[u], fbs[v])].push_back(Contrib{C_RELPOSE, rpb + i, 6 * u, 6 * v});
-        }
-    }
-    ATIME(9)
-    // diagonal pairs must exist for every f-block (they carry the damping, diag and rhs)
-    for (int k = fbBase; k < (int)B.fb_win.size(); ++k) pairs[std::make_pair(k, k)];
-    // tile-level structure of S and its symbolic LLT (fill within the envelope)
-    {
-      const int T = fpad / kTile;
-      std::vector<uint8_t> nz((size_t)T * T, 0);
-      for (int i = 0; i < T; ++i) nz[(size_t)i * T + i] = 1;
-      for (auto& kv : pairs) {
-        const int fa = kv.first.first, fb2 = kv.first.second;
-        const int na = B.fb_kind[fa] == 0 ? 6 : 9, nb = B.fb_kind[fb2] == 0 ? 6 : 9;
-        for (int ti = B.fb_off[fa] / kTile; ti <= (B.fb_off[fa] + na - 1) / kTile; ++ti)
-          for (int tj = B.fb_off[fb2] / kTile; tj <= (B.fb_off[fb2] + nb - 1) / kTile; ++tj)
-            nz[(size_t)std::max(ti, tj) * T + std::min(ti, tj)] = 1;
-      }
-      symbolicFill(nz, T);
-      // first band update of every tile (a step k < j with L_ik and L_jk non-zero): until then the
-      // factorisation reads the tile from the assembled S, afterwards from its working copy W
-      std::vector<int16_t> fu((size_t)T * T, kNoUpdate);
-      for (int i = 0; i < T; ++i)
-        for (int j = 0; j <= i; ++j)
-          for (int k = 0; k < j; ++k)
-            if (nz[(size_t)i * T + k] && nz[(size_t)j * T + k]) {
-              fu[(size_t)i * T + j] = (int16_t)k;
-              break;
-            }
-      // backward substitution split (nested dissection): the tiles of the left part [0, tL) and of
-      // the right part [tL, tS) share no non-zero tile, so once the separator's tiles [tS, T) are
-      // solved the two parts are independent (k_chol_bsub: one workgroup each)
-      int tL = rightAt / kTile, tS = sepAt / kTile;
-      bool split = ndLeft > 0 && tL > 0 && tS > tL;
-      for (int i = tL; split && i < tS; ++i)
-        for (int j = 0; j < tL; ++j)
-          if (nz[(size_t)i * T + j]) split = false;
-      B.win_bsplit.push_back(split ? tL : 0);
-      B.win_bsplit.push_back(split ? tS : 0);
-      B.win_defoff.push_back(B.defer_total);
-      if (split) B.defer_total += (int64_t)(T - tS) * (tS - tL) * kTile;
-      B.any_split = B.any_split || split;
-      B.tileFu.push_back(fu);
-      B.tileNz.push_back(nz);
-      B.tileT.push_back(T);
-    }
-    for (auto& kv : pairs) {
-      B.pair_win.push_back(w);
-      B.pair_fi.push_back(kv.first.first);
-      B.pair_fj.push_back(kv.first.second);
-      B.pair_cbegin.push_back((int)B.pair_contrib.size());
-      // contributions are grouped by kind (visits, landmark pairs, then factor blocks); the
-      // kernels stream each run separately
-      {
-        const int base = (int)B.pair_contrib.size();
-        int np = 0, nv = 0;
-        for (const Contrib& c : kv.second) { nv += c.type == C_VISIT; np += c.type == C_PAIR; }
-        for (size_t i = 0; i < kv.second.size(); ++i) {
-          const int t = kv.second[i].type;
-          const bool ok = (int)i < nv ? t == C_VISIT : ((int)i < nv + np ? t == C_PAIR : (t != C_VISIT && t != C_PAIR));
-          if (!ok) throw std::logic_error("pair contribution runs out of order");
-        }
-        B.pair_runs.push_back(base + nv);
-        B.pair_runs.push_back(base + nv + np);
-      }
-      B.pair_contrib.insert(B.pair_contrib.end(), kv.second.begin(), kv.second.end());
-    }
-  }
-  // tile-parallel schedule (cholSchedule): launch 0 factors every window's root tiles; launch
-  // l >= 1 runs the band updates of the steps scheduled there, each item (w, i, j, mode | k << 8):
-  // mode bit 0 = update of tile (i, j) by step k (panels formed from X_k), bit 1 = factor tile
-  // i (= j) afterwards (the item is its last update)
-  {
-    std::vector<std::vector<int32_t>> byLaunch(1);
-    for (int w = 0; w < B.n_win; ++w) {
-      const int T = B.tileT[w];
-      const auto& nz = B.tileNz[w];
-      std::vector<int> L, last;
-      const int nl = cholSchedule(nz, T, L, last);
-      B.n_chol_launches = std::max(B.n_chol_launches, nl);
-      if ((int)byLaunch.size() < nl) byLaunch.resize(nl);
-      bool first = true;
-      for (int d = 0; d < T; ++d)
-        if (last[(size_t)d * T + d] < 0) {
-          B.chol_root_items.push_back(w);
-          B.chol_root_items.push_back(d);
-          B.chol_root_items.push_back(first ? 1 : 0);
-          first = false;
-        }
-      for (int k = 0; k < T; ++k)
-        for (int i = k + 1; i < T; ++i)
-          if (nz[(size_t)i * T + k]) ++B.n_panels;
-      for (int k = 0; k < T; ++k)
-        for (int i = k + 1; i < T; ++i)
-          if (nz[(size_t)i * T + k])
-            for (int j = k + 1; j <= i; ++j)
-              if (nz[(size_t)j * T + k]) {
-                const bool fac = i == j && last[(size_t)i * T + i] == L[k];
-                auto& v = byLaunch[L[k]];
-                v.push_back(w); v.push_back(i); v.push_back(j); v.push_back((fac ? 3 : 1) | (k << 8));
-                ++B.n_band_updates;
-                if (i == j) ++B.n_band_updates_diag;
-              }
-    }
-    for (size_t l = 0; l < byLaunch.size(); ++l) {
-      B.chol_upd_begin.push_back((int)B.chol_upd_items.size() / 4);
-      B.chol_upd_items.insert(B.chol_upd_items.end(), byLaunch[l].begin(), byLaunch[l].end());
-    }
-    B.chol_upd_begin.push_back((int)B.chol_upd_items.size() / 4);
-  }
-  // assembly work lists: pose-pose pairs (one wavefront each, 4 per workgroup) are grouped so
-  // that workgroups b, b+8, ... (one XCD under round-robin placement; speed only) walk the pairs of
-  // the same windows and share their visit blocks in that XCD's L2
-  // Off-diagonal pairs with few contributions (no visits; partial blocks and factor blocks only)
-  // take a 16-lane quarter of a wavefront each (k_assemble_pp_light, 16 per workgroup).
-  {
-    constexpr int kXcd = 8;
-    const int nq = B.n_win >= kXcd ? kXcd : 1;
-    std::vector<std::vector<int32_t>> q(nq), ql(nq);
-    for (int k = 0; k < (int)B.pair_win.size(); ++k) {
-      const bool pp = B.fb_kind[B.pair_fi[k]] == 0 && B.fb_kind[B.pair_fj[k]] == 0;
-      const int kend = k + 1 < (int)B.pair_cbegin.size() ? B.pair_cbegin[k + 1] : (int)B.pair_contrib.size();
-      const bool light = B.n_win >= kManyWindows && B.pair_fi[k] != B.pair_fj[k] &&
-                         B.pair_runs[2 * k] == B.pair_cbegin[k] && kend - B.pair_cbegin[k] <= kAsmLightMax;
-      if (!pp) B.asm_sb_items.push_back(k);
-      else if (light) ql[B.pair_win[k] % nq].push_back(k);
-      else q[B.pair_win[k] % nq].push_back(k);
-    }
-    auto interleave = [&](std::vector<std::vector<int32_t>>& qq, int perWG, std::vector<int32_t>& out) {
-      std::vector<size_t> pos(nq, 0);
-      bool more = true;
-      while (more) {
-        more = false;
-        for (int x = 0; x < nq; ++x)
-          for (int i = 0; i < perWG; ++i) {
-            const bool has = pos[x] < qq[x].size();
-            out.push_back(has ? qq[x][pos[x]++] : -1);
-          }
-        for (int x = 0; x < nq; ++x) more = more || pos[x] < qq[x].size();
-      }
-      while (!out.empty() && out.back() < 0) out.pop_back();
-    };
-    interleave(q, 4, B.asm_pp_items);
-    interleave(ql, 16, B.asm_ppl_items);
-  }
-  for (int w = 0; w < B.n_win; ++w) {
-    B.win_tnzoff.push_back((int64_t)B.tile_nz.size());
-    B.tile_nz.insert(B.tile_nz.end(), B.tileNz[w].begin(), B.tileNz[w].end());
-    B.tile_fu.insert(B.tile_fu.end(), B.tileFu[w].begin(), B.tileFu[w].end());
-    const int T = B.tileT[w];
-    for (int k = 0; k < T; ++k) {
-      int np = 0;
-      for (int i = k + 1; i < T; ++i) np += B.tileNz[w][(size_t)i * T + k] ? 1 : 0;
-      B.max_panels = std::max(B.max_panels, np);
-    }
-  }
-  for (int w = 0; w < B.n_win; ++w) {
-    const int T = B.tileT[w];
-    for (int i = 0; i < T; ++i)
-      for (int j = 0; j <= i; ++j)
-        if (B.tileNz[w][(size_t)i * T + j]) { B.tile_items.push_back(w); B.tile_items.push_back(i); B.tile_items.push_back(j); }
-  }
-  B.lm_visit_begin.push_back((int)B.visit_pose.size());
-  B.lmg_begin.push_back((int)B.lm_win.size());  // groups: begin of each, then the end
-  {  // each window's groups are contiguous (built window by window)
-    B.win_lmg_range.assign(2 * (size_t)B.n_win, 0);
-    const int ng = (int)B.lmg_begin.size() - 1;
-    std::vector<int> first(B.n_win, -1), last(B.n_win, -1);
-    for (int g = 0; g < ng; ++g) {
-      const int w = B.lm_win[B.lmg_begin[g]];
-      if (first[w] < 0) first[w] = g;
-      last[w] = g;
-    }
-    for (int w = 0; w < B.n_win; ++w)
-      if (first[w] >= 0) {
-        B.win_lmg_range[2 * w] = first[w];
-        B.win_lmg_range[2 * w + 1] = last[w] + 1;
-      }
-  }
-  B.lmg_xbegin.push_back((int)B.xvisit_pose.size());
-  B.xvisit_obs_begin.push_back((int)B.xvisit_obs.size());
-  B.pe_obs_begin.push_back((int)B.pe_obs.size());
-  B.part_cbegin.push_back((int)B.part_contrib.size());
-  B.visit_obs_begin.push_back((int)B.obs_win.size());
-  B.imu_sbegin.push_back((int)B.imu_ts.size());
-  // host-evaluated factors share the IMU factors' per-factor arrays, after all of them
-  B.imu_blocks.insert(B.imu_blocks.end(), B.host_blocks.begin(), B.host_blocks.end());
-  B.imu_win.insert(B.imu_win.end(), B.host_win.begin(), B.host_win.end());
-  B.imu_flags.insert(B.imu_flags.end(), B.host_flags.begin(), B.host_flags.end());
-  B.fb_cbegin.push_back((int)B.fb_contrib.size());
-  B.pair_cbegin.push_back((int)B.pair_contrib.size());
-  {  // per-group record (two 16-byte loads; the terminal entry closes the last group)
-    const int ng = (int)B.lmg_begin.size() - 1;
-    B.lmg_info.assign(kLmgInfo * (size_t)(ng + 1), 0);
-    for (int g = 0; g <= ng; ++g) {
-      const int l0 = B.lmg_begin[g];
-      int32_t* r = &B.lmg_info[kLmgInfo * (size_t)g];
-      r[0] = l0;
-      r[1] = B.lm_visit_begin[l0];
-      r[2] = g < ng ? B.lm_win[l0] : -1;
-      r[3] = B.seg_gbegin[g];
-      r[4] = B.part_gbegin[g];
-      r[5] = B.part_cbegin[B.part_gbegin[g]];
-    }
-  }
-  ATIME(10)
-}
-
-// A single hipMalloc arena carved into the device arrays.
+// Offsets of the arrays of a one-off device allocation (imu_append, twopose_compute; the batch's
+// arena is laid out by layoutArena, plan.hpp).
 struct Arena {
-  char* base = nullptr;
-  size_t size = 0, used = 0;
-  std::vector<std::pair<size_t, size_t>> plan;
+  size_t size = 0;
   size_t reserve(size_t bytes) {
     const size_t off = (size + 255) & ~size_t(255);
     size = off + std::max<size_t>(bytes, 8);
     return off;
   }
-  template <class T>
-  T* at(size_t off) const { return reinterpret_cast<T*>(base + off); }
 };
 
 }  // namespace
@@ -1819,28 +494,16 @@ struct okvisgpu_ctx {
     const auto tb0 = std::chrono::steady_clock::now();
     {
       HostBatch nb;
-      // nested-dissection order where the tile-parallel or the split persistent schedule will run
-      // (at most one window per CU, setOptions): the chain of a window's factorisation is the
-      // latency there. The order is a function of the window and this flag only, so a window's
-      // bits depend on the batch just through it.
-      nb.nd = (int)probs.size() < cuCount;
+      nb.opt = planOptions((int)probs.size(), cuCount);
 #ifdef OKG_ND_OVERRIDE
-      if (const char* e = std::getenv("OKVISGPU_ND")) nb.nd = e[0] == '1';  // (development A/B builds only)
+      if (const char* e = std::getenv("OKVISGPU_ND")) nb.opt.nd = e[0] == '1';  // (development A/B builds only)
 #endif
-      // smaller landmark groups where a window's linearisation is a latency chain (fewWindows: one
-      // workgroup per group, ~16 us of phases for a 256-visit group): 64 visits / 16 landmarks
-      // (one S50 window: 36 -> 144 groups; steady iteration 0.3144 -> 0.3121 ms, S10 0.1580 ->
-      // 0.1541 ms, profiles/r06_lmg_ab.txt). Like the state order, a function of the batch size only.
-      if (fewWindows((int)probs.size(), cuCount)) {
-        nb.lmg_visits = 64;
-        nb.lmg_lms = 16;
-      }
 #ifdef OKG_LMG_OVERRIDE  // (development A/B builds only: OKVISGPU_LMG=visits,landmarks)
       if (const char* e = std::getenv("OKVISGPU_LMG")) {
         int v = 0, m = 0;
         if (std::sscanf(e, "%d,%d", &v, &m) == 2 && v >= 1 && v <= kLmGroupVisits && m >= 1 && m <= kLmGroupMax) {
-          nb.lmg_visits = v;
-          nb.lmg_lms = m;
+          nb.opt.lmg_visits = v;
+          nb.opt.lmg_lms = m;
         }
       }
 #endif
@@ -1848,142 +511,10 @@ struct okvisgpu_ctx {
       B = std::move(nb);
     }
     const auto tb1 = std::chrono::steady_clock::now();
-    // the uploaded arrays are laid out first (one contiguous host -> device copy from a pinned
-    // staging buffer), the scratch arrays after them (one memset); a scratch offset carries
-    // kScratchTag until the two regions are placed
-    constexpr size_t kScratchTag = size_t(1) << 62;
-    Arena A, AS;
-    DevProblem& D = P;
-    D = DevProblem{};
-    D.n_win = B.n_win;
-    D.n_pose = (int)B.pose_win.size();
-    D.n_sb = (int)B.sb_win.size();
-    D.n_lm = (int)B.lm_win.size();
-    D.n_obs = (int)B.obs_win.size();
-    D.n_visit = (int)B.visit_pose.size();
-    D.cu_count = cuCount;
-    D.lin_prep = -1;
-    D.n_imu = B.n_imu_total;
-    D.n_host = (int)B.hf.size();
-    D.n_fac = D.n_imu + D.n_host;
-    D.n_pprior = (int)B.pp_win.size();
-    D.n_sbprior = (int)B.sbp_win.size();
-    D.n_relpose = (int)B.rp_win.size();
-    D.n_cam = (int)(B.cam.size() / kCamDoubles);
-    D.n_fblock = (int)B.fb_win.size();
-    D.n_pair = (int)B.pair_win.size();
-    D.max_fpad = B.max_fpad;
-    D.max_tiles = B.max_fpad / kTile;
-    D.obs_stride = ((int64_t)D.n_obs + 63) / 64 * 64;
-    // ---- plan
-    struct Up { size_t off; const void* src; size_t bytes; };
-    std::vector<Up> ups;
-    auto upl = [&](const auto& vec) -> size_t {
-      using T = typename std::decay_t<decltype(vec)>::value_type;
-      const size_t bytes = vec.size() * sizeof(T);
-      const size_t off = A.reserve(bytes);
-      ups.push_back(Up{off, vec.data(), bytes});
-      return off;
-    };
-    auto scratch = [&](size_t bytes) { return kScratchTag | AS.reserve(bytes); };
-    const size_t o_pose0 = upl(B.pose), o_pose1 = upl(B.pose), o_sb0 = upl(B.sb), o_sb1 = upl(B.sb);
-    const size_t o_lm0 = upl(B.lm), o_lm1 = upl(B.lm), o_extr = upl(B.extr), o_cam = upl(B.cam);
-    const size_t o_pose_win = upl(B.pose_win), o_sb_win = upl(B.sb_win), o_lm_win = upl(B.lm_win);
-    const size_t o_pose_f = upl(B.pose_f), o_sb_f = upl(B.sb_f), o_lm_free = upl(B.lm_free);
-    const size_t o_pose_act = upl(B.pose_active), o_sb_act = upl(B.sb_active);
-    const size_t o_obs_pose = upl(B.obs_pose), o_obs_lm = upl(B.obs_lm), o_obs_cam = upl(B.obs_cam),
-                 o_obs_win = upl(B.obs_win), o_obs_flags = upl(B.obs_flags), o_obs_kp = upl(B.obs_kp),
-                 o_obs_L = upl(B.obs_L);
-    // every reprojection's square-root information diag(s, s) (okvis' keypoint-size information;
-    // +0.0 off the diagonal): k_eval_obs then reads s alone (8 instead of 32 bytes per observation)
-    // and forms the same products with the constant zeros, so the same bits
-    B.obs_iso = D.n_obs > 0;
-    B.obs_Ls.assign(std::max(1, D.n_obs), 0.0);
-    for (int o = 0; o < D.n_obs && B.obs_iso; ++o) {
-      const double* L = B.obs_L.data() + 4 * (size_t)o;
-      B.obs_iso = L[1] == 0.0 && !std::signbit(L[1]) && L[2] == 0.0 && !std::signbit(L[2]) && L[0] == L[3] &&
-                  std::signbit(L[0]) == std::signbit(L[3]);
-      B.obs_Ls[o] = L[0];
-    }
-    const size_t o_obs_Ls = upl(B.obs_Ls);
-    const size_t o_obs_lin0 = scratch(sizeof(double) * kObsLin * D.obs_stride);
-    const size_t o_obs_lin1 = scratch(sizeof(double) * kObsLin * D.obs_stride);
-    const size_t o_obs_cost0 = scratch(sizeof(double) * D.n_obs), o_obs_cost1 = scratch(sizeof(double) * D.n_obs);
-    const size_t o_grp_red = scratch(sizeof(double) * kGrpRed * std::max<size_t>(1, B.lmg_begin.size()));
-    const size_t o_lmvb = upl(B.lm_visit_begin), o_vpose = upl(B.visit_pose), o_vob = upl(B.visit_obs_begin),
-                 o_vlm = upl(B.visit_lm), o_lmg_b = upl(B.lmg_begin), o_lmg_info = upl(B.lmg_info);
-    const size_t o_lmV = scratch(sizeof(double) * 6 * D.n_lm), o_lmg = scratch(sizeof(double) * 3 * D.n_lm),
-                 o_lmVi = scratch(sizeof(double) * 9 * D.n_lm), o_lmz = scratch(sizeof(double) * 3 * D.n_lm);
-    D.n_seg = (int)B.seg_pose.size();
-    const size_t o_seg_gb = upl(B.seg_gbegin), o_seg_pose = upl(B.seg_pose), o_seg_rg = upl(B.seg_range),
-                 o_vslot = upl(B.visit_slot);
-    D.n_part = (int)B.part_cbegin.size() - 1;
-    const size_t o_pgb = upl(B.part_gbegin), o_pcb2 = upl(B.part_cbegin), o_pcon = upl(B.part_contrib),
-                 o_partS = scratch(sizeof(double) * 36 * std::max(1, D.n_part));
-    const size_t o_shg = scratch(sizeof(double) * kSegHG * D.n_seg), o_suz = scratch(sizeof(double) * kSegUz * D.n_seg);
-    D.n_xvisit = (int)B.xvisit_pose.size();
-    D.n_pe = (int)B.pe_pose.size();
-    const size_t o_cpose = upl(B.cam_pose), o_xvp = upl(B.xvisit_pose), o_xvl = upl(B.xvisit_lm),
-                 o_xvob = upl(B.xvisit_obs_begin), o_xvo = upl(B.xvisit_obs), o_xvs = upl(B.xvisit_slot),
-                 o_lmgx = upl(B.lmg_xbegin), o_pep = upl(B.pe_pose), o_pee = upl(B.pe_ext), o_peob = upl(B.pe_obs_begin),
-                 o_peo = upl(B.pe_obs), o_peH = scratch(sizeof(double) * 36 * std::max(1, D.n_pe));
-    const size_t o_imu_blocks = upl(B.imu_blocks), o_imu_win = upl(B.imu_win), o_imu_flags = upl(B.imu_flags),
-                 o_imu_t0 = upl(B.imu_t0), o_imu_t1 = upl(B.imu_t1), o_imu_sb = upl(B.imu_sbegin),
-                 o_imu_ts = upl(B.imu_ts), o_imu_ga = upl(B.imu_ga), o_imu_par = upl(B.imu_par),
-                 o_imu_state = upl(B.imu_state);
-    const size_t o_imu_lin0 = scratch(sizeof(double) * kImuLin * D.n_fac),
-                 o_imu_lin1 = scratch(sizeof(double) * kImuLin * D.n_fac);
-    const size_t o_imu_cost0 = scratch(sizeof(double) * D.n_fac), o_imu_cost1 = scratch(sizeof(double) * D.n_fac),
-                 o_imu_jv = scratch(sizeof(double) * 3 * D.n_fac),
-                 o_imu_H = scratch(sizeof(double) * kImuHess * D.n_fac);
-    const size_t o_whr = upl(B.win_host_range), o_host_in = scratch(sizeof(double) * kHostIn * D.n_host),
-                 o_host_out = scratch(sizeof(double) * kHostOut * D.n_host);
-    const size_t o_pp_block = upl(B.pp_block), o_pp_win = upl(B.pp_win), o_pp_meas = upl(B.pp_meas),
-                 o_pp_L = upl(B.pp_L);
-    const size_t o_pp_lin0 = scratch(sizeof(double) * 42 * D.n_pprior), o_pp_lin1 = scratch(sizeof(double) * 42 * D.n_pprior),
-                 o_pp_cost0 = scratch(sizeof(double) * D.n_pprior), o_pp_cost1 = scratch(sizeof(double) * D.n_pprior),
-                 o_pp_jv = scratch(sizeof(double) * 3 * D.n_pprior);
-    const size_t o_sbp_block = upl(B.sbp_block), o_sbp_win = upl(B.sbp_win), o_sbp_meas = upl(B.sbp_meas),
-                 o_sbp_L = upl(B.sbp_L);
-    const size_t o_sbp_lin0 = scratch(sizeof(double) * 90 * D.n_sbprior),
-                 o_sbp_lin1 = scratch(sizeof(double) * 90 * D.n_sbprior),
-                 o_sbp_cost0 = scratch(sizeof(double) * D.n_sbprior), o_sbp_cost1 = scratch(sizeof(double) * D.n_sbprior),
-                 o_sbp_jv = scratch(sizeof(double) * 3 * D.n_sbprior);
-    const size_t o_rp_blocks = upl(B.rp_blocks), o_rp_win = upl(B.rp_win), o_rp_flags = upl(B.rp_flags),
-                 o_rp_kind = upl(B.rp_kind),
-                 o_rp_dx = upl(B.rp_dx), o_rp_J = upl(B.rp_J), o_rp_lp = upl(B.rp_lp);
-    const size_t o_rp_lin0 = scratch(sizeof(double) * kRelPoseLin * D.n_relpose),
-                 o_rp_lin1 = scratch(sizeof(double) * kRelPoseLin * D.n_relpose),
-                 o_rp_cost0 = scratch(sizeof(double) * D.n_relpose), o_rp_cost1 = scratch(sizeof(double) * D.n_relpose),
-                 o_rp_jv = scratch(sizeof(double) * 3 * D.n_relpose), o_wrpr = upl(B.win_rp_range);
-    const size_t o_wfoff = upl(B.win_foff), o_wfdim = upl(B.win_fdim), o_wfpad = upl(B.win_fpad),
-                 o_wsoff = upl(B.win_soff), o_wlinv = upl(B.win_linvoff), o_wfwd = upl(B.win_fwdoff), o_wpr = upl(B.win_pose_range), o_wsr = upl(B.win_sb_range),
-                 o_wlr = upl(B.win_lm_range), o_wlgr = upl(B.win_lmg_range), o_wor = upl(B.win_obs_range), o_wir = upl(B.win_imu_range),
-                 o_wppr = upl(B.win_pp_range), o_wsbpr = upl(B.win_sbp_range);
-    const size_t o_fbw = upl(B.fb_win), o_fbk = upl(B.fb_kind), o_fbi = upl(B.fb_index), o_fbo = upl(B.fb_off),
-                 o_fbcb = upl(B.fb_cbegin), o_fbc = upl(B.fb_contrib);
-    const size_t o_pw = upl(B.pair_win), o_pfi = upl(B.pair_fi), o_pfj = upl(B.pair_fj), o_pcb = upl(B.pair_cbegin),
-                 o_pc = upl(B.pair_contrib);
-    const size_t o_pruns = upl(B.pair_runs);
-    const size_t o_tnz = upl(B.tile_nz), o_tnzoff = upl(B.win_tnzoff), o_tfu = upl(B.tile_fu);
-    const size_t o_app = upl(B.asm_pp_items), o_asb = upl(B.asm_sb_items), o_appl = upl(B.asm_ppl_items);
-    const size_t o_ti = upl(B.tile_items);
-    const size_t o_cri = upl(B.chol_root_items), o_cui = upl(B.chol_upd_items), o_cub = upl(B.chol_upd_begin);
-    const size_t o_wsgap = upl(B.win_sgap), o_wbsp = upl(B.win_bsplit), o_wdef = upl(B.win_defoff);
-    const size_t nf = std::max(1, B.f_total), nl3 = std::max<size_t>(1, (size_t)3 * D.n_lm);
-    const size_t o_S = scratch(sizeof(double) * std::max<int64_t>(1, B.s_total));
-    const size_t o_W = scratch(sizeof(double) * std::max<int64_t>(1, B.s_total));
-    const size_t o_Linv = scratch(sizeof(double) * std::max<int64_t>(1, B.linv_total));
-    const size_t o_fwd = scratch(sizeof(double) * std::max<int64_t>(1, B.fwd_total));
-    const size_t o_defer = scratch(sizeof(double) * std::max<int64_t>(1, B.defer_total));
-    size_t of[10], ol[7];
-    for (int i = 0; i < 10; ++i) of[i] = scratch(sizeof(double) * nf);
-    for (int i = 0; i < 7; ++i) ol[i] = scratch(sizeof(double) * nl3);
-    const size_t o_st = scratch(sizeof(WinState) * D.n_win);
-    const size_t o_self = scratch(sizeof(DevProblem));
-    // ---- allocate (reusing the arena while the batch fits) + upload
-    const size_t upSize = (A.size + 255) & ~size_t(255);
-    const size_t total = upSize + AS.size;
+    const ArenaLayout L = layoutArena(B, cuCount, P);
+    // ---- allocate (reusing the arena while the batch fits) + upload: one contiguous host -> device
+    // copy of the uploaded region from the pinned staging buffer, one memset of the scratch region
+    const size_t upBytes = L.region_bytes[0], total = L.arenaBytes();
     if (!arena || total > arenaCap) {
       if (arena) {
         HIPCHK(hipFree(arena));
@@ -1995,110 +526,21 @@ struct okvisgpu_ctx {
     }
     arenaBytes = total;
     char* base = static_cast<char*>(arena);
-    if (A.size > hostStageBytes) {
-      if (hostStage) HIPCHK(hipHostFree(hostStage));
-      hostStage = nullptr;
-      hostStageBytes = 0;
-      HIPCHK(hipHostMalloc(&hostStage, A.size, hipHostMallocDefault));
-      hostStageBytes = A.size;
-    }
-    HIPCHK(hipStreamSynchronize(stream));  // the staging buffer is free (previous upload done)
+    char* stage = paramStage(upBytes);  // (synchronises: the previous upload is done)
     const auto tb2 = std::chrono::steady_clock::now();
-    for (const Up& u : ups)
-      if (u.bytes) std::memcpy(static_cast<char*>(hostStage) + u.off, u.src, u.bytes);
+    for (const ArenaBinding& b : L.table)
+      if (b.region == 0 && b.bytes) std::memcpy(stage + b.off, b.src, b.bytes);
     const auto tb3 = std::chrono::steady_clock::now();
     if (timing) {
       auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
       std::fprintf(stderr, "okvisgpu build: analyse %.3f ms, layout+alloc %.3f ms, stage %.3f ms (%zu B)\n", ms(tb0, tb1),
-                   ms(tb1, tb2), ms(tb2, tb3), A.size);
+                   ms(tb1, tb2), ms(tb2, tb3), upBytes);
     }
-    if (A.size) HIPCHK(hipMemcpyAsync(base, hostStage, A.size, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemsetAsync(base + upSize, 0, AS.size, stream));
+    if (upBytes) HIPCHK(hipMemcpyAsync(base, stage, upBytes, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(base + L.scratchBase(), 0, L.region_bytes[1], stream));
     sNeedsInit = true;
-    auto place = [&](size_t off) { return (off & kScratchTag) ? upSize + (off & ~kScratchTag) : off; };
-    auto dp = [&](size_t off) { return reinterpret_cast<double*>(base + place(off)); };
-    auto ip = [&](size_t off) { return reinterpret_cast<int32_t*>(base + place(off)); };
-    auto lp = [&](size_t off) { return reinterpret_cast<int64_t*>(base + place(off)); };
-    auto up = [&](size_t off) { return reinterpret_cast<uint8_t*>(base + place(off)); };
-    D.pose[0] = dp(o_pose0); D.pose[1] = dp(o_pose1); D.sb[0] = dp(o_sb0); D.sb[1] = dp(o_sb1);
-    D.lm[0] = dp(o_lm0); D.lm[1] = dp(o_lm1); D.extr = dp(o_extr); D.cam = dp(o_cam);
-    D.pose_win = ip(o_pose_win); D.sb_win = ip(o_sb_win); D.lm_win = ip(o_lm_win);
-    D.pose_f = ip(o_pose_f); D.sb_f = ip(o_sb_f); D.lm_free = up(o_lm_free);
-    D.pose_active = up(o_pose_act); D.sb_active = up(o_sb_act);
-    D.obs_pose = ip(o_obs_pose); D.obs_lm = ip(o_obs_lm); D.obs_cam = ip(o_obs_cam); D.obs_win = ip(o_obs_win);
-    D.obs_flags = up(o_obs_flags); D.obs_kp = dp(o_obs_kp); D.obs_L = dp(o_obs_L);
-    D.obs_Ls = dp(o_obs_Ls); D.obs_iso = B.obs_iso;
-    D.obs_lin[0] = dp(o_obs_lin0); D.obs_lin[1] = dp(o_obs_lin1);
-    D.obs_cost[0] = dp(o_obs_cost0); D.obs_cost[1] = dp(o_obs_cost1); D.grp_red = dp(o_grp_red);
-    D.lm_visit_begin = ip(o_lmvb); D.visit_pose = ip(o_vpose); D.visit_obs_begin = ip(o_vob); D.visit_lm = ip(o_vlm);
-    D.lm_V = dp(o_lmV); D.lm_g = dp(o_lmg); D.lm_Linv = dp(o_lmVi); D.lm_zz = dp(o_lmz);
-    D.part_gbegin = ip(o_pgb); D.part_cbegin = ip(o_pcb2); D.part_contrib = ip(o_pcon); D.part_S = dp(o_partS);
-    D.seg_hg = dp(o_shg); D.seg_uz = dp(o_suz);
-    D.seg_gbegin = ip(o_seg_gb); D.seg_pose = ip(o_seg_pose); D.seg_range = ip(o_seg_rg); D.visit_slot = ip(o_vslot);
-    D.cam_pose = ip(o_cpose);
-    D.xvisit_pose = ip(o_xvp); D.xvisit_lm = ip(o_xvl); D.xvisit_obs_begin = ip(o_xvob); D.xvisit_obs = ip(o_xvo);
-    D.xvisit_slot = ip(o_xvs); D.lmg_xbegin = ip(o_lmgx);
-    D.pe_pose = ip(o_pep); D.pe_ext = ip(o_pee); D.pe_obs_begin = ip(o_peob); D.pe_obs = ip(o_peo); D.pe_H = dp(o_peH);
-    D.lmg_info = ip(o_lmg_info);
-    D.lmg_begin = ip(o_lmg_b); D.n_lmg = B.lmg_begin.empty() ? 0 : (int)B.lmg_begin.size() - 1;
-    D.imu_blocks = ip(o_imu_blocks); D.imu_win = ip(o_imu_win); D.imu_flags = up(o_imu_flags);
-    D.imu_t0 = lp(o_imu_t0); D.imu_t1 = lp(o_imu_t1); D.imu_sbegin = ip(o_imu_sb); D.imu_ts = lp(o_imu_ts);
-    D.imu_ga = dp(o_imu_ga); D.imu_par = dp(o_imu_par); D.imu_state = dp(o_imu_state);
-    D.imu_lin[0] = dp(o_imu_lin0); D.imu_lin[1] = dp(o_imu_lin1);
-    D.imu_cost[0] = dp(o_imu_cost0); D.imu_cost[1] = dp(o_imu_cost1); D.imu_jv = dp(o_imu_jv);
-    D.imu_H = dp(o_imu_H);
-    D.win_host_range = ip(o_whr); D.host_in = dp(o_host_in); D.host_out = dp(o_host_out);
-    D.pp_block = ip(o_pp_block); D.pp_win = ip(o_pp_win); D.pp_meas = dp(o_pp_meas); D.pp_L = dp(o_pp_L);
-    D.pp_lin[0] = dp(o_pp_lin0); D.pp_lin[1] = dp(o_pp_lin1); D.pp_cost[0] = dp(o_pp_cost0);
-    D.pp_cost[1] = dp(o_pp_cost1); D.pp_jv = dp(o_pp_jv);
-    D.sbp_block = ip(o_sbp_block); D.sbp_win = ip(o_sbp_win); D.sbp_meas = dp(o_sbp_meas); D.sbp_L = dp(o_sbp_L);
-    D.sbp_lin[0] = dp(o_sbp_lin0); D.sbp_lin[1] = dp(o_sbp_lin1); D.sbp_cost[0] = dp(o_sbp_cost0);
-    D.sbp_cost[1] = dp(o_sbp_cost1); D.sbp_jv = dp(o_sbp_jv);
-    D.win_foff = ip(o_wfoff); D.win_fdim = ip(o_wfdim); D.win_fpad = ip(o_wfpad); D.win_soff = lp(o_wsoff);
-    D.win_pose_range = ip(o_wpr); D.win_sb_range = ip(o_wsr); D.win_lm_range = ip(o_wlr); D.win_lmg_range = ip(o_wlgr);
-    D.win_obs_range = ip(o_wor); D.win_imu_range = ip(o_wir); D.win_pp_range = ip(o_wppr);
-    D.win_sbp_range = ip(o_wsbpr);
-    D.win_rp_range = ip(o_wrpr);
-    D.rp_blocks = ip(o_rp_blocks); D.rp_win = ip(o_rp_win); D.rp_flags = up(o_rp_flags); D.rp_kind = up(o_rp_kind);
-    D.rp_dx = dp(o_rp_dx); D.rp_J = dp(o_rp_J); D.rp_lp = dp(o_rp_lp);
-    D.rp_lin[0] = dp(o_rp_lin0); D.rp_lin[1] = dp(o_rp_lin1);
-    D.rp_cost[0] = dp(o_rp_cost0); D.rp_cost[1] = dp(o_rp_cost1); D.rp_jv = dp(o_rp_jv);
-    D.fb_win = ip(o_fbw); D.fb_kind = ip(o_fbk); D.fb_index = ip(o_fbi); D.fb_off = ip(o_fbo);
-    D.fb_cbegin = ip(o_fbcb); D.fb_contrib = reinterpret_cast<const Contrib*>(base + place(o_fbc));
-    D.pair_win = ip(o_pw); D.pair_fi = ip(o_pfi); D.pair_fj = ip(o_pfj); D.pair_cbegin = ip(o_pcb);
-    D.pair_contrib = reinterpret_cast<const Contrib*>(base + place(o_pc));
-    D.pair_runs = ip(o_pruns);
-    D.tile_nz = reinterpret_cast<const uint8_t*>(base + place(o_tnz));
-    D.tile_fu = reinterpret_cast<const int16_t*>(base + place(o_tfu));
-    D.win_tnzoff = reinterpret_cast<const int64_t*>(base + place(o_tnzoff));
-    D.chol_root_items = ip(o_cri);
-    D.n_chol_roots = (int)B.chol_root_items.size() / 3;
-    D.n_chol_launches = B.n_chol_launches;
-    D.chol_upd_items = ip(o_cui); D.chol_upd_begin = ip(o_cub);
-    D.h_upd_begin = B.chol_upd_begin.data();
-    D.win_sgap = ip(o_wsgap);
-    D.win_bsplit = ip(o_wbsp);
-    D.chol_schedule = 1;
-    D.asm_pp_items = ip(o_app); D.asm_sb_items = ip(o_asb);
-    D.n_asm_pp = (int)B.asm_pp_items.size(); D.n_asm_sb = (int)B.asm_sb_items.size();
-    D.asm_ppl_items = ip(o_appl); D.n_asm_ppl = (int)B.asm_ppl_items.size();
-    D.tile_items = ip(o_ti);
-    D.n_tiles = (int)(B.tile_items.size() / 3);
-    D.S = dp(o_S);
-    D.W = dp(o_W);
-    D.Linv = dp(o_Linv);
-    D.win_linvoff = lp(o_wlinv);
-    D.fwdF = dp(o_fwd);
-    D.chol_defer = dp(o_defer);
-    D.win_defoff = lp(o_wdef);
-    D.win_fwdoff = lp(o_wfwd);
-    double** fv[10] = {&D.sF, &D.diagF, &D.hdF, &D.gF, &D.rhsF, &D.yF, &D.gnF, &D.dgF, &D.vF, &D.stepF};
-    for (int i = 0; i < 10; ++i) *fv[i] = dp(of[i]);
-    double** lv[7] = {&D.sL, &D.diagL, &D.stepL, &D.yL, &D.gnL, &D.dgL, &D.vL};
-    for (int i = 0; i < 7; ++i) *lv[i] = dp(ol[i]);
-    D.gL = D.lm_g;  // the landmark gradient is the accumulated J_l^T r
-    D.st = reinterpret_cast<WinState*>(base + place(o_st));
-    D.self = reinterpret_cast<const DevProblem*>(base + place(o_self));
+    L.patch(base);
+    P.gL = P.lm_g;  // the landmark gradient is the accumulated J_l^T r
     HIPCHK(hipStreamSynchronize(stream));
     uploadDescriptor();
     ensureHostBuffers();
@@ -2864,7 +1306,7 @@ int okvisgpu_plan_window(const okvisgpu_problem* p, int32_t nested_dissection, i
   if (!p) return OKVISGPU_ERR_INVALID_ARGUMENT;
   try {
     HostBatch B;
-    B.nd = nested_dissection != 0;
+    B.opt.nd = nested_dissection != 0;
 #ifdef OKG_ANALYSE_TIMING
     for (double& x : g_atime) x = 0.0;
     g_alast = std::chrono::steady_clock::now();
@@ -2872,7 +1314,7 @@ int okvisgpu_plan_window(const okvisgpu_problem* p, int32_t nested_dissection, i
     analyse({p}, {}, B);
 #ifdef OKG_ANALYSE_TIMING
     std::fprintf(stderr, "analyse ms:");
-    for (int i = 0; i < 11; ++i) std::fprintf(stderr, " [%d] %.3f", i, g_atime[i]);
+    for (int i = 0; i < kAnalysePhases; ++i) std::fprintf(stderr, " [%d] %.3f", i, g_atime[i]);
     std::fprintf(stderr, "\n");
 #endif
     const int T = B.tileT[0], fpad = B.win_fpad[0];

@@ -208,7 +208,7 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_time_kernel", "okvisgpu_eval_relpose", "okvisgpu_twopose_compute",
     "okvisgpu_graph_load", "okvisgpu_graph_problem", "okvisgpu_graph_ids", "okvisgpu_graph_destroy",
     "okvisgpu_graph_save", "okvisgpu_get_stats", "okvisgpu_synth_true_extrinsics", "okvisgpu_imu_append",
-    "okvisgpu_eval_host", "okvisgpu_plan_window", "okvisgpu_loss_evaluate",
+    "okvisgpu_eval_host", "okvisgpu_plan_window", "okvisgpu_loss_evaluate", "okvisgpu_plan_digest",
 ]
 N_PHASES = 15
 
@@ -268,6 +268,8 @@ def lib():
         L.okvisgpu_graph_save.argtypes = [C.POINTER(Problem), _lp, C.c_char_p]
         L.okvisgpu_get_stats.argtypes = [C.c_void_p, C.POINTER(ProblemStats)]
         L.okvisgpu_plan_window.argtypes = [C.POINTER(Problem), C.c_int32, _lp, C.POINTER(C.c_uint8), _ip, _ip]
+        L.okvisgpu_plan_digest.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, _lp, C.c_int32, _ip, C.c_char_p,
+                                           _ip, _lp, C.POINTER(C.c_uint64)]
         L.okvisgpu_imu_append.argtypes = [C.c_void_p, C.POINTER(ImuAppendBatch), _ip]
         L.okvisgpu_twopose_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _dp, _dp]
         L.okvisgpu_loss_evaluate.argtypes = [C.POINTER(Loss), C.c_double, _dp]
@@ -298,6 +300,32 @@ def plan_window(problem, nested_dissection):
     out["step_launch"] = launch
     out["natural"] = nat
     return out
+
+
+PLAN_DIGEST_TOTALS = ("f_total", "s_total", "linv_total", "fwd_total", "defer_total", "max_fpad", "max_panels",
+                      "n_chol_launches", "n_panels", "n_band_updates", "n_band_updates_diag", "any_split", "obs_iso",
+                      "upload_bytes", "scratch_bytes")
+
+
+def plan_digest(problems, cu_count):
+    """okvisgpu_plan_digest (host only): the plan of a batch on a device of cu_count CUs as its
+    scalar totals and, in arena-table order, [name, region (0 uploaded, 1 scratch), bytes,
+    FNV-1a-64 of the uploaded bytes as hex (None for scratch)] per device array."""
+    L = lib()
+    arr = (Problem * len(problems))(*problems)
+    totals, n = (C.c_int64 * 16)(), C.c_int32(0)
+    rc = L.okvisgpu_plan_digest(arr, len(problems), int(cu_count), totals, 0, C.byref(n), None, None, None, None)
+    if rc != 0:
+        raise RuntimeError(f"okvisgpu_plan_digest failed ({rc})")
+    cap = n.value
+    names = C.create_string_buffer(32 * cap)
+    region, nbytes, hashes = (C.c_int32 * cap)(), (C.c_int64 * cap)(), (C.c_uint64 * cap)()
+    rc = L.okvisgpu_plan_digest(arr, len(problems), int(cu_count), totals, cap, C.byref(n), names, region, nbytes, hashes)
+    if rc != 0 or n.value != cap:
+        raise RuntimeError(f"okvisgpu_plan_digest failed ({rc})")
+    entries = [[names.raw[32 * i:32 * i + 32].split(b"\0")[0].decode(), int(region[i]), int(nbytes[i]),
+                f"{hashes[i]:016x}" if region[i] == 0 else None] for i in range(cap)]
+    return {"totals": {k: int(v) for k, v in zip(PLAN_DIGEST_TOTALS, totals)}, "entries": entries}
 
 
 def default_options(**kw) -> Options:
