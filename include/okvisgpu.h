@@ -504,6 +504,18 @@ int okvisgpu_plan_digest(const okvisgpu_problem* problems, int32_t n_windows, in
                          int32_t capacity, int32_t* n_entries, char* names, int32_t* region, int64_t* bytes,
                          uint64_t* hash);
 
+/* Host-only: what the batch size decides about the launches of a solve on a device of cu_count
+ * compute units (no device, no context; development, tests/test_launch_regime.py). any_split: a
+ * window has a nested-dissection split; persistent_fits / pipe_fits: the persistent / pipelined
+ * Cholesky's LDS holds the largest window; cholesky_schedule: options.cholesky_schedule;
+ * serial_graph (0 / 1), lin_prep (0) and graph_iters (K) are the measurement overrides
+ * OKVISGPU_SERIAL_GRAPH, OKVISGPU_LIN_PREP and OKVISGPU_GRAPH_ITERS, -1 = not set.
+ *   regime[7]: few windows, many windows, one-stream graph, GN prep inside the linearisation,
+ *              gradient test inside the assembly, iterations per graph, resolved Cholesky schedule */
+int okvisgpu_launch_regime(int32_t n_windows, int32_t cu_count, int32_t any_split, int32_t persistent_fits,
+                           int32_t pipe_fits, int32_t cholesky_schedule, int32_t serial_graph, int32_t lin_prep,
+                           int32_t graph_iters, int32_t* regime);
+
 /* Copy device parameter values back into the caller's host arrays without solving. */
 int okvisgpu_get_params(okvisgpu_ctx* ctx);
 

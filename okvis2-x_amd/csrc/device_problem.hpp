@@ -33,15 +33,10 @@ constexpr int kObsLin = 8;   // r (2) | A = L Jh C_CW (2x3), Cauchy-scaled
 constexpr int kSegHG = 28;   // per visit segment: H = sum J_p^T J_p (21, sym packed) | g = sum J_p^T r (6) | pad
 constexpr int kSegUz = 8;    // per visit segment: sum U z (6) | pad
 constexpr int kLmGroupVisits = 256;  // k_lm_visit: visits of one landmark group (one workgroup)
-// A batch of at most a quarter window per CU: the latency regime (per-window reductions at 1,024
-// threads, fused launches of the iteration's independent small kernels).
-__host__ __device__ constexpr bool fewWindows(int nWin, int cuCount) { return 4 * nWin <= cuCount; }
 constexpr int kLmGroupMax = 64;      // landmarks per group
 constexpr int kLmPartStage = 2048;   // landmark-pair products per group (staged in LDS)
 constexpr int kAsmLightMax = 24;     // contributions of a pose-pose pair assembled by a 16-lane quarter
-constexpr int kManyWindows = 64;     // batches from this size use the fewer-workgroup layouts (light
-                                     // pairs, several S tiles per workgroup); below it latency rules
-constexpr int kLmgInfo = 8;          // ints per landmark-group record (lmg_info)
+constexpr int kLmgInfo = 8;         // ints per landmark-group record (lmg_info)
 constexpr int kImuHess = 465 + 30;  // packed upper J^T J (30x30) | J^T r
 constexpr int kGrpRed = 8;    // per landmark group: jcc | jgg | jcg | gg | nn | gn | pad
 constexpr int kVisitZ = 18;   // per visit: Z = s_p W s_l L^-T (6x3), k_lm_visit LDS only
@@ -99,8 +94,8 @@ struct DevProblem {
   const DevProblem* self;          // device-resident copy of this descriptor (what kernels receive)
   int32_t n_win, n_pose, n_sb, n_lm, n_obs, n_visit, n_imu, n_pprior, n_sbprior, n_cam;
   int32_t cu_count;                // compute units of the device (persistent-style grids)
-  int32_t lin_prep;                // host only: GN prep inside the linearisation launch (1 / 0),
-                                   // fixed per solve (lin_runs_prep); -1 = not yet decided
+  int8_t few, many, lin_prep, pad_;  // host only, read by the launchers, never by a kernel: the
+                                   // LaunchRegime (plan.hpp) the runtime decided, with chol_schedule
   int32_t n_fblock, n_pair;
   int32_t max_fpad, max_tiles;     // largest padded reduced dimension / its 64-tile count
   int64_t obs_stride;              // plane stride of the obs linearisation SoA (>= n_obs)
@@ -291,7 +286,7 @@ struct DevProblem {
   const int32_t* chol_upd_items;
   const int32_t* chol_upd_begin;
   const int32_t* h_upd_begin;
-  int32_t chol_schedule;             // 1 persistent per window, 2 tile-parallel (host-resolved)
+  int32_t chol_schedule;             // host only: LaunchRegime::chol_schedule
   const uint8_t* tile_nz;            // per window T x T (row-major) structural non-zero flags of L
   const int16_t* tile_fu;            // per window T x T (same offsets): the first step whose band update
                                      // writes tile (i, j) (kNoUpdate if none): before it the tile is read from S

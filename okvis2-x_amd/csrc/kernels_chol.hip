@@ -397,10 +397,10 @@ void launch_cholesky_split_b(const DevProblem& P, hipStream_t s) {
   hipLaunchKernelGGL(k_cholesky<2>, dim3(P.n_win), dim3(256), sizeof(double) * P.max_fpad, s, P.self);
 }
 
-bool cholesky_persistent_fits(int max_fpad, size_t lds_per_block) {
+size_t cholesky_persistent_lds() {
   hipFuncAttributes attr;
-  if (hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(k_cholesky<0>)) != hipSuccess) return false;
-  return attr.sharedSizeBytes + sizeof(double) * (size_t)max_fpad <= lds_per_block;
+  if (hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(k_cholesky<0>)) != hipSuccess) return ~size_t(0) >> 1;
+  return attr.sharedSizeBytes;
 }
 
 void launch_cholesky(const DevProblem& P, hipStream_t s) {

@@ -362,10 +362,10 @@ __global__ __launch_bounds__(512, 1) void k_cholesky_pipe(const DevProblem* __re
   PCLK_REPORT(T)
 }
 
-bool cholesky_pipe_fits(int max_fpad, size_t lds_per_block) {
+size_t cholesky_pipe_lds() {
   hipFuncAttributes attr;
-  if (hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(k_cholesky_pipe<1>)) != hipSuccess) return false;
-  return attr.sharedSizeBytes + sizeof(double) * (size_t)max_fpad <= lds_per_block;
+  if (hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(k_cholesky_pipe<1>)) != hipSuccess) return ~size_t(0) >> 1;
+  return attr.sharedSizeBytes;
 }
 
 // split: schedule 5 (launch A pipelined per nested-dissection part, launch B = k_cholesky<2>)

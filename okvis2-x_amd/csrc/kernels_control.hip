@@ -469,7 +469,7 @@ void launch_jv(const DevProblem& P, hipStream_t s) {
   if (jvBlocks(P) > 0) hipLaunchKernelGGL(k_jv, dim3(jvBlocks(P)), dim3(256), 0, s, P.self);
 }
 void launch_reduce(const DevProblem& P, int mode, hipStream_t s) {
-  if (fewWindows(P.n_win, P.cu_count)) hipLaunchKernelGGL(k_reduce<kRBFew>, dim3(P.n_win), dim3(kRBFew), 0, s, P.self, mode);
+  if (P.few) hipLaunchKernelGGL(k_reduce<kRBFew>, dim3(P.n_win), dim3(kRBFew), 0, s, P.self, mode);
   else hipLaunchKernelGGL(k_reduce<kRBBatch>, dim3(P.n_win), dim3(kRBBatch), 0, s, P.self, mode);
 }
 // (256 threads for every batch size: the few-window iteration runs the same test inside the
@@ -478,7 +478,7 @@ void launch_gradnorm(const DevProblem& P, int lin_mode, hipStream_t s) {
   hipLaunchKernelGGL(k_gradnorm<kRBBatch>, dim3(P.n_win), dim3(kRBBatch), 0, s, P.self, lin_mode);
 }
 void launch_dogleg(const DevProblem& P, hipStream_t s) {
-  if (fewWindows(P.n_win, P.cu_count)) hipLaunchKernelGGL(k_dogleg<kRBFew>, dim3(P.n_win), dim3(kRBFew), 0, s, P.self);
+  if (P.few) hipLaunchKernelGGL(k_dogleg<kRBFew>, dim3(P.n_win), dim3(kRBFew), 0, s, P.self);
   else hipLaunchKernelGGL(k_dogleg<kRBBatch>, dim3(P.n_win), dim3(kRBBatch), 0, s, P.self);
 }
 

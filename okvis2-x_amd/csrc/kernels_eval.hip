@@ -1271,11 +1271,10 @@ void launch_eval_imu(const DevProblem& P, int mode, hipStream_t s) {
   const int nb = (P.n_imu + kImuPerWG - 1) / kImuPerWG + (np + 63) / 64;
   if (nb > 0) hipLaunchKernelGGL(k_eval_imu<false>, dim3(nb), dim3(64), 0, s, P.self, mode);
 }
-void launch_eval_priors(const DevProblem& P, int mode, hipStream_t s) {}  // (in launch_eval_imu)
 // The IMU factors (and priors / edges) as the solve's evaluation runs them: one or two windows
 // through k_eval_few's IMU chunking (no observation workgroups), else k_eval_imu (okvisgpu_time_kernel).
 void launch_eval_imu_as_solved(const DevProblem& P, int mode, hipStream_t s) {
-  if (fewWindows(P.n_win, P.cu_count) && P.n_win <= kImuFewChunkWindows) {
+  if (P.few && P.n_win <= kImuFewChunkWindows) {
     const int np = P.n_pprior + P.n_sbprior + P.n_relpose;
     const int nb = (P.n_imu + kImuPerWG - 1) / kImuPerWG + (np + 63) / 64;
     if (nb > 0) hipLaunchKernelGGL(k_eval_few<kImuKFew>, dim3(nb), dim3(64), 0, s, P.self, mode, 0);
@@ -1283,18 +1282,17 @@ void launch_eval_imu_as_solved(const DevProblem& P, int mode, hipStream_t s) {
   }
   launch_eval_imu(P, mode, s);
 }
+void launch_eval_few(const DevProblem& P, int mode, hipStream_t s) {
+  const int np = P.n_pprior + P.n_sbprior + P.n_relpose;
+  const int nObs = (P.n_obs + 63) / 64, nb = nObs + (P.n_imu + kImuPerWG - 1) / kImuPerWG + (np + 63) / 64;
+  if (nb <= 0) return;
+  if (P.n_win <= kImuFewChunkWindows) hipLaunchKernelGGL(k_eval_few<kImuKFew>, dim3(nb), dim3(64), 0, s, P.self, mode, nObs);
+  else hipLaunchKernelGGL(k_eval_few<kImuK>, dim3(nb), dim3(64), 0, s, P.self, mode, nObs);
+}
 void launch_eval(const DevProblem& P, int mode, hipStream_t s) {
-  if (fewWindows(P.n_win, P.cu_count)) {
-    const int np = P.n_pprior + P.n_sbprior + P.n_relpose;
-    const int nObs = (P.n_obs + 63) / 64, nb = nObs + (P.n_imu + kImuPerWG - 1) / kImuPerWG + (np + 63) / 64;
-    if (nb <= 0) return;
-    if (P.n_win <= kImuFewChunkWindows) hipLaunchKernelGGL(k_eval_few<kImuKFew>, dim3(nb), dim3(64), 0, s, P.self, mode, nObs);
-    else hipLaunchKernelGGL(k_eval_few<kImuK>, dim3(nb), dim3(64), 0, s, P.self, mode, nObs);
-    return;
-  }
+  if (P.few) return launch_eval_few(P, mode, s);
   launch_eval_obs(P, mode, s);
   launch_eval_imu(P, mode, s);
-  launch_eval_priors(P, mode, s);
 }
 
 void launch_imu_append(const DevProblem& P, hipStream_t s) {

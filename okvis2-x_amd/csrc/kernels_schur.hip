@@ -22,7 +22,7 @@
 //                 (the landmarks' back substitution and vectors: k_lm_backsub_jv, kernels_backsub.hip).
 #include <algorithm>
 #include <cfloat>
-#include <cstdlib>
+#include <type_traits>
 
 #include "dev_clock.hpp"
 #include "device_problem.hpp"
@@ -655,16 +655,6 @@ __global__ __launch_bounds__(kLmGroupVisits, OKG_LMV_OCC) void k_lin_few(const D
   if (PREP && !gmem(P.st + gmem(P.lmg_info)[kLmgInfo * b + 2])->accepted) lmVisitGroup<2, EXT>(P, b);
   else lmVisitGroup<1, EXT>(P, b);
 }
-// Few windows run the GN prep inside the linearisation launch (k_lin_few<.., true>); env override
-// OKVISGPU_LIN_PREP=0 (measurements). The runtime decides once per solve (P.lin_prep, set in
-// okvisgpu_solve_begin before the initial launches and the graph capture), so the initial
-// linearisation and the captured iterations always agree on where the prep runs.
-bool lin_runs_prep(const DevProblem& P) {
-  if (P.lin_prep >= 0) return P.lin_prep != 0;
-  if (!fewWindows(P.n_win, P.cu_count)) return false;
-  const char* e = std::getenv("OKVISGPU_LIN_PREP");
-  return !(e && e[0] == '0');
-}
 
 // A 16-lane group per f-block (16 per 256-thread workgroup; a pose has ~10 contributions): lanes
 // stride over the contribution list, then a fixed xor-tree reduction over the group (deterministic).
@@ -818,24 +808,19 @@ __device__ __forceinline__ bool gnSelect(const DevProblem& P, int w) {
 
 // Clears the structurally non-zero tiles of S (kZeroTiles consecutive tiles per workgroup; padded
 // diagonal = 1). Since round 4 the factorisation works in W and never writes S, and the assembly
-// overwrites its blocks every iteration, so S is cleared once per build (mode 2: every window,
-// no state test) instead of every iteration. Modes 0 (windows about to assemble) and 1 (every
-// window not done) are kept for the eager entry points' semantics.
-constexpr int kZeroTiles = 4;  // (one per workgroup below kManyWindows windows: latency)
-__global__ __launch_bounds__(256) void k_zero_S(const DevProblem* __restrict__ Pp, int per, int tail) {
+// overwrites its blocks every iteration, so S is cleared once per build (every window, no state
+// test) instead of every iteration.
+constexpr int kZeroTiles = 4;  // (one per workgroup below many windows: latency)
+__global__ __launch_bounds__(256) void k_zero_S(const DevProblem* __restrict__ Pp, int per) {
   const DevProblem& P = *Pp;
   const auto ti3 = gmem(P.tile_items);
   for (int u = 0; u < per; ++u) {
     const int item = blockIdx.x * per + u;
     if (item >= P.n_tiles) return;
     const int w = ti3[3 * item], ti = ti3[3 * item + 1], tj = ti3[3 * item + 2];
-    const auto gst = gmem(P.st + w);
-    const int sDone = gst->done, sNeed = gst->need_gn | tail, sFail = gst->gn_failed & (tail ^ 1);
     const int fpad = gmem(P.win_fpad)[w], fdim = gmem(P.win_fdim)[w];
     const int g0 = gmem(P.win_sgap)[2 * w], g1 = g0 + gmem(P.win_sgap)[2 * w + 1];
     const int64_t soff = gmem(P.win_soff)[w];
-    asm volatile("" ::"v"(fpad), "v"(fdim), "v"(g0), "v"(g1), "v"(soff));
-    if (tail != 2 && ((sDone != 0) | (sNeed == 0) | (sFail != 0))) continue;  // uniform
     double* S = P.S + soff;
     for (int e = threadIdx.x; e < kTile * kTile / 2; e += 256) {
       const int rl = e >> 5, cl = 2 * (e & 31);
@@ -1185,24 +1170,23 @@ __device__ __forceinline__ void asmPairsSb(const DevProblem& P, int bid) {
 __global__ __launch_bounds__(256) void k_assemble_sb(const DevProblem* __restrict__ Pp) { asmPairsSb(*Pp, (int)blockIdx.x); }
 
 // ------------------------------------------------------------------------------------ launchers
+// f(std::true_type / std::false_type) for a run-time flag that selects a template instance
+template <class F>
+static void withFlag(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
 void launch_lm_visit(const DevProblem& P, int mode, hipStream_t s) {
   if (P.n_lmg <= 0) return;
   const dim3 g(P.n_lmg), b(kLmGroupVisits);
-  if (mode == 2 && P.n_win >= kManyWindows) {  // window loop over resident workgroups
-    const dim3 gw(std::min(P.n_win, P.cu_count * OKG_LMV_OCC));
-    if (P.n_xvisit > 0) hipLaunchKernelGGL((k_lm_prep_windows<true>), gw, b, 0, s, P.self);
-    else hipLaunchKernelGGL((k_lm_prep_windows<false>), gw, b, 0, s, P.self);
-    return;
-  }
-  if (P.n_xvisit > 0) {
-    if (mode == 0) hipLaunchKernelGGL((k_lm_visit<0, true>), g, b, 0, s, P.self);
-    else if (mode == 1) hipLaunchKernelGGL((k_lm_visit<1, true>), g, b, 0, s, P.self);
-    else hipLaunchKernelGGL((k_lm_visit<2, true>), g, b, 0, s, P.self);
-  } else {
-    if (mode == 0) hipLaunchKernelGGL((k_lm_visit<0, false>), g, b, 0, s, P.self);
-    else if (mode == 1) hipLaunchKernelGGL((k_lm_visit<1, false>), g, b, 0, s, P.self);
-    else hipLaunchKernelGGL((k_lm_visit<2, false>), g, b, 0, s, P.self);
-  }
+  withFlag(P.n_xvisit > 0, [&](auto ext) {
+    constexpr bool EXT = decltype(ext)::value;
+    if (mode == 2 && P.many)  // window loop over resident workgroups
+      hipLaunchKernelGGL((k_lm_prep_windows<EXT>), dim3(std::min(P.n_win, P.cu_count * OKG_LMV_OCC)), b, 0, s, P.self);
+    else if (mode == 0) hipLaunchKernelGGL((k_lm_visit<0, EXT>), g, b, 0, s, P.self);
+    else if (mode == 1) hipLaunchKernelGGL((k_lm_visit<1, EXT>), g, b, 0, s, P.self);
+    else hipLaunchKernelGGL((k_lm_visit<2, EXT>), g, b, 0, s, P.self);
+  });
 }
 void launch_assemble_pp(const DevProblem& P, hipStream_t s) {
   if (P.n_asm_pp > 0) hipLaunchKernelGGL(k_assemble_pp, dim3((P.n_asm_pp + 3) / 4), dim3(256), 0, s, P.self);
@@ -1220,40 +1204,33 @@ void launch_lm_blocks(const DevProblem& P, int lin_mode, hipStream_t s) {
 void launch_fgrad(const DevProblem& P, int lin_mode, hipStream_t s) {
   if (P.n_fblock <= 0) return;
   const dim3 g((P.n_fblock + 256 / kFgLanes - 1) / (256 / kFgLanes));
-  if (fewWindows(P.n_win, P.cu_count)) hipLaunchKernelGGL(k_fgrad<2>, g, dim3(256), 0, s, P.self, lin_mode);
+  if (P.few) hipLaunchKernelGGL(k_fgrad<2>, g, dim3(256), 0, s, P.self, lin_mode);
   else hipLaunchKernelGGL(k_fgrad<1>, g, dim3(256), 0, s, P.self, lin_mode);
 }
 void launch_imu_hess(const DevProblem& P, int lin_mode, hipStream_t s) {
   if (P.n_fac > 0) hipLaunchKernelGGL(k_imu_hess, dim3((P.n_fac + 3) / 4), dim3(256), 0, s, P.self, lin_mode);
 }
-void launch_linearization_blocks(const DevProblem& P, int lin_mode, hipStream_t s) {
-  if (lin_mode == 1 && fewWindows(P.n_win, P.cu_count)) {
-    const int nb = P.n_lmg + (P.n_fac + 3) / 4;
-    if (nb > 0) {
-      const bool prep = lin_runs_prep(P);
-      if (P.n_xvisit > 0) {
-        if (prep) hipLaunchKernelGGL((k_lin_few<true, true>), dim3(nb), dim3(kLmGroupVisits), 0, s, P.self, lin_mode);
-        else hipLaunchKernelGGL((k_lin_few<true, false>), dim3(nb), dim3(kLmGroupVisits), 0, s, P.self, lin_mode);
-      } else {
-        if (prep) hipLaunchKernelGGL((k_lin_few<false, true>), dim3(nb), dim3(kLmGroupVisits), 0, s, P.self, lin_mode);
-        else hipLaunchKernelGGL((k_lin_few<false, false>), dim3(nb), dim3(kLmGroupVisits), 0, s, P.self, lin_mode);
-      }
-    }
-    if (P.n_pe > 0) hipLaunchKernelGGL(k_pose_extr, dim3((P.n_pe + 255) / 256), dim3(256), 0, s, P.self, lin_mode);
-  } else {
-    launch_lm_blocks(P, lin_mode, s);
-    launch_imu_hess(P, lin_mode, s);
-  }
-  launch_fgrad(P, lin_mode, s);
+// Few windows, linearisation at the accepted point: landmark groups and IMU J^T J as one launch
+// (k_lin_few), with the GN prep of the windows not accepted where the regime places it there
+void launch_lin_few(const DevProblem& P, hipStream_t s) {
+  const int nb = P.n_lmg + (P.n_fac + 3) / 4;
+  if (nb > 0)
+    withFlag(P.n_xvisit > 0, [&](auto ext) {
+      withFlag(P.lin_prep != 0, [&](auto prep) {
+        hipLaunchKernelGGL((k_lin_few<decltype(ext)::value, decltype(prep)::value>), dim3(nb), dim3(kLmGroupVisits), 0, s,
+                           P.self, 1);
+      });
+    });
+  if (P.n_pe > 0) hipLaunchKernelGGL(k_pose_extr, dim3((P.n_pe + 255) / 256), dim3(256), 0, s, P.self, 1);
 }
 void launch_lm_prep(const DevProblem& P, hipStream_t s) { launch_lm_visit(P, 2, s); }
-void launch_zero_S(const DevProblem& P, hipStream_t s, int tail) {
-  const int per = P.n_win >= kManyWindows ? kZeroTiles : 1;
-  if (P.n_tiles > 0) hipLaunchKernelGGL(k_zero_S, dim3((P.n_tiles + per - 1) / per), dim3(256), 0, s, P.self, per, tail);
+void launch_zero_S(const DevProblem& P, hipStream_t s) {
+  const int per = P.many ? kZeroTiles : 1;
+  if (P.n_tiles > 0) hipLaunchKernelGGL(k_zero_S, dim3((P.n_tiles + per - 1) / per), dim3(256), 0, s, P.self, per);
 }
 // Few windows: the three assembly kernels as one launch (block ranges; the kernels are independent:
 // disjoint pairs of S), two graph nodes fewer on a single window's latency chain.
-// With grad (the captured few-window iteration, runtime.cpp launchIteration): one more block per
+// With grad (the captured few-window iteration, runtime.cpp fewSteps): one more block per
 // window runs the gradient tolerance test of the previous iteration's linearisation (gradnorm.hpp,
 // 256 threads as everywhere): it reads the parameters, the gradient and the window state, which
 // the assembly does not write, and the assembly needs no result of it (a window it ends is
@@ -1272,20 +1249,10 @@ static void launchAssembleFew(const DevProblem& P, hipStream_t s, bool grad) {
   if (nA + nG > 0) hipLaunchKernelGGL(k_assemble_few, dim3(nA + nG), dim3(256), 0, s, P.self, nH, nL, nA);
 }
 void launch_assemble(const DevProblem& P, hipStream_t s) {
-  if (fewWindows(P.n_win, P.cu_count)) {
-    launchAssembleFew(P, s, false);
-    return;
-  }
+  if (P.few) return launchAssembleFew(P, s, false);
   launch_assemble_pp(P, s);
   launch_assemble_sb(P, s);
 }
 void launch_assemble_gradnorm_few(const DevProblem& P, hipStream_t s) { launchAssembleFew(P, s, true); }
-void launch_gn_reduce(const DevProblem& P, hipStream_t s) {
-  launch_lm_prep(P, s);
-  launch_assemble(P, s);
-}
-void launch_gn_backsub(const DevProblem& P, hipStream_t s) {
-  launch_lm_backsub(P, s);  // (the f-blocks' GN vectors are written by the Cholesky's back substitution)
-}
 
 }  // namespace okg

@@ -1,5 +1,8 @@
 // launch.hpp — host-side launchers of the gfx950 kernels (one stream, graph-capturable: no
-// allocation, no synchronisation, no host reads inside any launcher).
+// allocation, no synchronisation, no host reads inside any launcher). A launcher only launches:
+// grids come from the descriptor's counts, and where the batch size picks a kernel form it reads
+// the regime the runtime decided (DevProblem few / many / lin_prep / chol_schedule; launchRegime,
+// plan.hpp). The order of an iteration's launches is the runtime's step table.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,10 +12,10 @@
 namespace okg {
 
 // evaluation (kernels_eval.hip); mode 0 current, 1 candidate, 2 initial, 3 initial without loss
-void launch_eval(const DevProblem& P, int mode, hipStream_t s);
+void launch_eval(const DevProblem& P, int mode, hipStream_t s);      // few: launch_eval_few, else obs + imu
+void launch_eval_few(const DevProblem& P, int mode, hipStream_t s);  // observations, IMU, priors, edges as one launch
 void launch_eval_obs(const DevProblem& P, int mode, hipStream_t s);
 void launch_eval_imu(const DevProblem& P, int mode, hipStream_t s);
-void launch_eval_priors(const DevProblem& P, int mode, hipStream_t s);
 void launch_eval_imu_as_solved(const DevProblem& P, int mode, hipStream_t s);  // (okvisgpu_time_kernel)
 // ImuError::append for a batch (P: n_imu, imu_blocks {0, f, 0, f}, imu_t0 = old t1, imu_t1 = new t1,
 // imu_sbegin / imu_ts / imu_ga = appended samples, imu_par (one row), imu_state, sb[0] = biases)
@@ -23,20 +26,16 @@ void launch_host_gather(const DevProblem& P, int mode, hipStream_t s);
 void launch_host_scatter(const DevProblem& P, hipStream_t s);
 
 // landmark / reduced-system kernels (kernels_schur.hip); lin_mode 0 = init, 1 = accepted only
-void launch_linearization_blocks(const DevProblem& P, int lin_mode, hipStream_t s);
-void launch_gn_reduce(const DevProblem& P, hipStream_t s);    // lm_prep + assemble (S is initialised once per build, ensureS)
-void launch_gn_backsub(const DevProblem& P, hipStream_t s);   // landmark back substitution + gn vectors
 void launch_lm_blocks(const DevProblem& P, int lin_mode, hipStream_t s);
 void launch_imu_hess(const DevProblem& P, int lin_mode, hipStream_t s);
 void launch_fgrad(const DevProblem& P, int lin_mode, hipStream_t s);
 void launch_lm_prep(const DevProblem& P, hipStream_t s);
-// few windows: the GN prep runs inside the linearisation after a step (launch_linearization_blocks),
-// so the captured iteration does not start with it and the initial linearisation ends with it
-bool lin_runs_prep(const DevProblem& P);
-// the non-zero tiles of S: tail = 0 of the windows about to assemble; tail = 1 of every window not
-// done (end of the captured iteration, S dead)
-void launch_zero_S(const DevProblem& P, hipStream_t s, int tail = 0);
-void launch_assemble(const DevProblem& P, hipStream_t s);
+// few windows, after a step: landmark groups + IMU J^T J as one launch; with P.lin_prep also the GN
+// prep of the windows not accepted, so the captured iteration does not start with it and the
+// initial linearisation ends with it
+void launch_lin_few(const DevProblem& P, hipStream_t s);
+void launch_zero_S(const DevProblem& P, hipStream_t s);  // the non-zero tiles of S, once per build
+void launch_assemble(const DevProblem& P, hipStream_t s);  // few: one launch, else pp + sb
 void launch_lm_backsub(const DevProblem& P, hipStream_t s);  // kernels_backsub.hip: + landmark dogleg vectors, J*v
 void launch_assemble_gradnorm_few(const DevProblem& P, hipStream_t s);  // few windows: + the gradient test
 void launch_assemble_pp(const DevProblem& P, hipStream_t s);
@@ -45,9 +44,10 @@ void launch_lm_visit(const DevProblem& P, int mode, hipStream_t s);  // 0/1: lin
 
 // dense factorisation + both triangular solves, one persistent workgroup per window
 // (kernels_chol.hip)
-// persistent Cholesky: does its LDS (static + the window's solve vector) fit a workgroup?
-bool cholesky_persistent_fits(int max_fpad, size_t lds_per_block);
-bool cholesky_pipe_fits(int max_fpad, size_t lds_per_block);  // (kernels_chol_pipe.hip)
+// static LDS of the persistent / the pipelined kernel (the window's solve vector comes on top as
+// dynamic LDS); a value nothing fits if the query fails
+size_t cholesky_persistent_lds();
+size_t cholesky_pipe_lds();  // (kernels_chol_pipe.hip)
 void launch_cholesky(const DevProblem& P, hipStream_t s);
 void launch_cholesky_pipe(const DevProblem& P, hipStream_t s, bool split);
 void launch_cholesky_split_b(const DevProblem& P, hipStream_t s);  // k_cholesky<2> (kernels_chol.hip)

@@ -29,16 +29,60 @@ std::chrono::steady_clock::time_point g_alast;
 
 PlanOptions planOptions(int n_windows, int cu_count) {
   // nested-dissection order where the tile-parallel or the split persistent schedule will run
-  // (at most one window per CU, setOptions): the chain of a window's factorisation is the
+  // (below one window per CU, launchRegime): the chain of a window's factorisation is the
   // latency there.
   PlanOptions o;
-  o.nd = n_windows < cu_count;
+  o.nd = belowOneWindowPerCu(n_windows, cu_count);
   // smaller landmark groups where a window's linearisation is a latency chain (fewWindows: one
   // workgroup per group, ~16 us of phases for a 256-visit group): 64 visits / 16 landmarks
   // (one S50 window: 36 -> 144 groups; steady iteration 0.3144 -> 0.3121 ms, S10 0.1580 ->
   // 0.1541 ms, profiles/r06_lmg_ab.txt).
   if (fewWindows(n_windows, cu_count)) { o.lmg_visits = 64; o.lmg_lms = 16; }
   return o;
+}
+
+LaunchRegime launchRegime(int n, int cu, bool any_split, bool persistent_fits, bool pipe_fits, int schedule,
+                          int serial_override, int prep_override, int iters_override) {
+  LaunchRegime r;
+  r.few = fewWindows(n, cu);
+  r.many = manyWindows(n);
+  // Below one window per CU the graph is one stream (a cross-stream edge of the graph costs ~10 us,
+  // more than the overlap of a single window's small kernels gains: S50 1488 -> 1614 it/s); a full
+  // batch keeps the fork streams (2,048 S50 windows: 135.7k -> 138.5k window-it/s).
+  r.serial_graph = serial_override >= 0 ? serial_override != 0 : belowOneWindowPerCu(n, cu);
+  r.lin_prep = r.few && prep_override != 0;
+  r.fused_gradnorm = r.few && r.serial_graph;
+  // consecutive launches of one graph are ~8 us apart on the device (4.5 % of the S10 single-window
+  // iteration; batches +0.2-0.3 %, r05bk)
+  r.graph_iters = iters_override < 0 ? 4 : std::max(1, std::min(iters_override, 64));
+  // Cholesky schedule (measured on MI355X, S50 windows, bench window-it/s, round 4 with the
+  // nested-dissection order (nd) below one window per CU: 64 windows: schedule 1 65.2k, 2 (nd)
+  // 72.2k; 128: 1 103.6k, 3 (nd) 107.9k, 2 (nd) 98.2k; 256: 1 159.7k, 3 (nd) 152.8k; 512: 1
+  // 186.5k, 3 (nd) 166.0k; gpurun_out r04g / r04h nd_probe; round 5, the pipelined two-team
+  // kernel (4), gpurun_out r05g: 64: 2 74.1k, 4 67.0k; 128: 3 110.1k, 4 105.7k; 256: 1 161.0k,
+  // 4 170.1k; 512: 1 186.7k, 4 178.7k; the split schedule with pipelined parts (5), r05s: 64: 2
+  // 73.9k, 3 70.4k, 5 73.7k; 128: 3 109.8k, 5 114.5k; 192: 4 133.6k, 3 127.3k, 5 120.7k; one S50
+  // window: 2 2,765, 5 2,336, 3 2,233, 4 1,858 it/s): below half a window per CU the
+  // tile-parallel launches spread each window over many CUs; at half a window per CU the split
+  // schedule with each part pipelined; up to one window per CU the pipelined kernel (its step is
+  // the factor plus one panel and one update); from there one persistent workgroup per window,
+  // two per CU. (A wave-specialised kernel and a persistent variant with the panel tiles in LDS were
+  // measured slower at every batch size and removed in round 4; a two-window pipelined
+  // workgroup, round 5, ran 166.8k against 199.4k at 2,048 windows and was removed.)
+  int s = schedule >= 1 && schedule <= 5 ? schedule
+          : 2 * n < cu                   ? 2
+          : 2 * n <= cu && any_split     ? 5
+          : n <= cu                      ? 4
+                                         : 1;
+  if (s == 3 && !any_split) s = 1;  // (no window with a nested-dissection split)
+  if (s == 5 && !any_split) s = 4;
+  // the persistent kernels keep the window's rhs / y in dynamic LDS next to their static tiles:
+  // a reduced dimension beyond what fits falls back, in the end to the tile-parallel launches
+  if (s == 5 && !(pipe_fits && persistent_fits)) s = 3;
+  if (s == 4 && !pipe_fits) s = 1;
+  if ((s == 1 || s == 3) && !persistent_fits) s = 2;
+  r.chol_schedule = s;
+  return r;
 }
 
 // ---- tile-level symbolic factorisation and the tile-parallel launch schedule -------------------
@@ -1042,7 +1086,7 @@ void assemblyLists(HostBatch& B) {
   for (int k = 0; k < (int)B.pair_win.size(); ++k) {
     const bool pp = B.fb_kind[B.pair_fi[k]] == 0 && B.fb_kind[B.pair_fj[k]] == 0;
     const int kend = k + 1 < (int)B.pair_cbegin.size() ? B.pair_cbegin[k + 1] : (int)B.pair_contrib.size();
-    const bool light = B.n_win >= kManyWindows && B.pair_fi[k] != B.pair_fj[k] &&
+    const bool light = manyWindows(B.n_win) && B.pair_fi[k] != B.pair_fj[k] &&
                        B.pair_runs[2 * k] == B.pair_cbegin[k] && kend - B.pair_cbegin[k] <= kAsmLightMax;
     if (!pp) B.asm_sb_items.push_back(k);
     else if (light) ql[B.pair_win[k] % nq].push_back(k);
@@ -1208,7 +1252,7 @@ struct LayoutBuilder {
 
 ArenaLayout layoutArena(const HostBatch& B, int cu_count, DevProblem& D) {
   D = DevProblem{};
-  D.n_win = B.n_win; D.cu_count = cu_count; D.lin_prep = -1; D.chol_schedule = 1;
+  D.n_win = B.n_win; D.cu_count = cu_count;
   D.n_pose = (int)B.pose_win.size(); D.n_sb = (int)B.sb_win.size(); D.n_lm = (int)B.lm_win.size();
   D.n_obs = (int)B.obs_win.size(); D.n_visit = (int)B.visit_pose.size(); D.n_cam = (int)(B.cam.size() / kCamDoubles);
   D.n_imu = B.n_imu_total; D.n_host = (int)B.hf.size(); D.n_fac = D.n_imu + D.n_host;
@@ -1324,4 +1368,16 @@ extern "C" int okvisgpu_plan_digest(const okvisgpu_problem* problems, int32_t n_
   } catch (const ArgError&) {
     return OKVISGPU_ERR_INVALID_ARGUMENT;
   }
+}
+
+// ---- okvisgpu_launch_regime (okvisgpu.h): launchRegime() on plain ints ---------------------------
+extern "C" int okvisgpu_launch_regime(int32_t n_windows, int32_t cu_count, int32_t any_split, int32_t persistent_fits,
+                                      int32_t pipe_fits, int32_t cholesky_schedule, int32_t serial_graph,
+                                      int32_t lin_prep, int32_t graph_iters, int32_t* regime) {
+  if (n_windows <= 0 || cu_count <= 0 || !regime) return OKVISGPU_ERR_INVALID_ARGUMENT;
+  const okg::LaunchRegime r = okg::launchRegime(n_windows, cu_count, any_split != 0, persistent_fits != 0, pipe_fits != 0,
+                                                cholesky_schedule, serial_graph, lin_prep, graph_iters);
+  const int32_t v[7] = {r.few, r.many, r.serial_graph, r.lin_prep, r.fused_gradnorm, r.graph_iters, r.chol_schedule};
+  std::copy(v, v + 7, regime);
+  return OKVISGPU_OK;
 }

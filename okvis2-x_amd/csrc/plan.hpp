@@ -22,13 +22,41 @@ namespace okg {
 struct ArgError { std::string msg; };          // -> OKVISGPU_ERR_INVALID_ARGUMENT
 struct UnsupportedError { std::string msg; };  // -> OKVISGPU_ERR_UNSUPPORTED
 
-// What a batch's size decides on a device of cu_count CUs (planOptions): a function of these two
-// numbers only, so a window's bits depend on the batch just through them.
+// The batch-size predicates, on a device of cu CUs. Few: at most a quarter window per CU, the latency
+// regime (per-window reductions at 1,024 threads, fused launches of the iteration's independent small
+// kernels, small landmark groups). Many: the fewer-workgroup layouts (light pairs, several S tiles
+// per workgroup, the GN prep as a window loop); below it latency rules. Below one window per CU:
+// nested-dissection order, one-stream graph.
+inline bool fewWindows(int n, int cu) { return 4 * n <= cu; }
+inline bool manyWindows(int n) { return n >= 64; }
+inline bool belowOneWindowPerCu(int n, int cu) { return n < cu; }
+
+// What a batch's size decides about the plan (planOptions): a function of the window count and the
+// CU count only, so a window's bits depend on the batch just through them.
 struct PlanOptions {
   bool nd = false;  // order the windows' states for the tile-parallel schedule (nested dissection)
   int lmg_visits = kLmGroupVisits, lmg_lms = kLmGroupMax;  // landmark-group bounds (k_lm_visit workgroups)
 };
 PlanOptions planOptions(int n_windows, int cu_count);
+
+// What a batch's size decides about the launches (launchRegime): the one place the launch structure
+// of a solve is chosen; the runtime stores it and the launchers read it (DevProblem's host-only
+// fields). None of it changes a solve's bits.
+struct LaunchRegime {
+  bool few = false, many = false;
+  bool serial_graph = true;     // the captured iteration on one stream (else fork streams)
+  bool lin_prep = false;        // the GN prep runs inside the linearisation launch (k_lin_few<.., true>)
+  bool fused_gradnorm = false;  // the gradient test runs inside the next assembly launch (k_assemble_few)
+  int graph_iters = 4;          // iterations captured as one graph beside the single-iteration graph
+  int chol_schedule = 1;        // 1 persistent, 2 tile-parallel, 3 split persistent, 4 pipelined, 5 split pipelined
+};
+// Pure integer logic (okvisgpu_launch_regime, tests/test_launch_regime.py). persistent_fits /
+// pipe_fits: the kernels' LDS holds the largest window (cholesky_persistent_lds / _pipe_lds);
+// schedule: options.cholesky_schedule (1..5, else automatic); the overrides are the parsed
+// measurement switches OKVISGPU_SERIAL_GRAPH (0 / 1), OKVISGPU_LIN_PREP (0) and
+// OKVISGPU_GRAPH_ITERS (K), -1 = not set.
+LaunchRegime launchRegime(int n_windows, int cu_count, bool any_split, bool persistent_fits, bool pipe_fits,
+                          int schedule, int serial_override, int prep_override, int iters_override);
 
 // Host mirror of everything uploaded (built by analyse()).
 struct HostBatch {

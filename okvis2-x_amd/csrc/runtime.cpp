@@ -160,24 +160,35 @@ struct okvisgpu_ctx {
   DevProblem P{};
   void* arena = nullptr;
   size_t arenaBytes = 0;
-  hipGraphExec_t iterGraph = nullptr;
-  // kGraphIters iterations captured as one graph as well (iterGraphK): consecutive launches of one
-  // graph are ~8 us apart on the device (4.5 % of the S10 single-window iteration; batches +0.2-0.3 %,
-  // r05bk), so solve_iterate runs n iterations as n / K launches of it and n mod K of the single one.
-  static constexpr int kGraphIters = 4;
-  hipGraphExec_t iterGraphK = nullptr;
-  int graphIters = 1;
+  // The captured iteration, and graphIters = regime.graph_iters iterations captured as one graph as
+  // well (iterGraphK): solve_iterate runs n iterations as n / K launches of it and n mod K of the single one.
+  hipGraphExec_t iterGraph = nullptr, iterGraphK = nullptr;
+  int graphIters = 1;  // the K iterGraphK was captured with
   int cuCount = 256;
-  size_t ldsPerBlock = 65536;
-  bool persistentFits() const { return cholesky_persistent_fits(P.max_fpad, ldsPerBlock); }
-  bool pipeFits() const { return cholesky_pipe_fits(P.max_fpad, ldsPerBlock); }
+  size_t ldsPerBlock = 65536, persistentLds = 0, pipeLds = 0;  // device LDS; static LDS of the two Cholesky kernels
+  // The launch regime (plan.hpp), decided by setOptions() at solve_begin and, with default options,
+  // after a build; the launchers read its copy in P. The measurement switches are parsed here, once
+  // per decision: OKVISGPU_SERIAL_GRAPH=0|1, OKVISGPU_LIN_PREP=0, OKVISGPU_GRAPH_ITERS=<K>.
+  LaunchRegime regime;
+  void decideRegime(int schedule) {
+    // the persistent kernels keep the window's rhs / y in dynamic LDS next to their static tiles
+    auto fits = [&](size_t staticLds) { return staticLds + sizeof(double) * (size_t)P.max_fpad <= ldsPerBlock; };
+    const char *ser = std::getenv("OKVISGPU_SERIAL_GRAPH"), *prep = std::getenv("OKVISGPU_LIN_PREP"),
+               *gi = std::getenv("OKVISGPU_GRAPH_ITERS");
+    const LaunchRegime r = launchRegime(P.n_win, cuCount, B.any_split, fits(persistentLds), fits(pipeLds), schedule,
+                                        ser && (ser[0] == '0' || ser[0] == '1') ? ser[0] - '0' : -1,
+                                        prep && prep[0] == '0' ? 0 : -1, gi && *gi ? std::max(0, std::atoi(gi)) : -1);
+    if (r.chol_schedule != regime.chol_schedule) dropGraph();
+    regime = r;
+    P.few = r.few; P.many = r.many; P.lin_prep = r.lin_prep; P.chol_schedule = r.chol_schedule;
+  }
   // S is cleared by the build's arena memset; its padded diagonal (rows >= fdim) is set once per
-  // build before the first factorisation (k_zero_S setup mode). The factorisation works in W and
-  // the assembly overwrites its blocks, so S needs no clearing per iteration.
+  // build before the first factorisation (k_zero_S). The factorisation works in W and the assembly
+  // overwrites its blocks, so S needs no clearing per iteration.
   bool sNeedsInit = true;
   void ensureS(hipStream_t s) {
     if (!sNeedsInit) return;
-    launch_zero_S(P, s, 2);
+    launch_zero_S(P, s);
     sNeedsInit = false;
   }
   bool haveProblem = false;
@@ -247,47 +258,6 @@ struct okvisgpu_ctx {
     inSolve = false;
     tPost = nowS() - t;
     fillSummaries(st, sums);
-  }
-
-  // One trust-region iteration as eager launches on the context's stream with HIP events between
-  // the phases (the captured graph's kernels in the same order: the same bits); ms[phase] += the
-  // phase's device time. okvisgpu_profile_iteration and the verbose solve.
-  void profiledIteration(double* ms) {
-    hipStream_t s = stream;
-    std::vector<hipEvent_t> ev;
-    std::vector<int> phaseOf;
-    auto mark = [&](int phase) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      HIPCHK(hipEventRecord(e, s));
-      ev.push_back(e);
-      phaseOf.push_back(phase);
-    };
-    mark(-1);
-    launch_lm_prep(P, s); mark(0);
-    mark(1);  // (S is no longer cleared per iteration: phase kept for the ABI's phase list)
-    launch_assemble(P, s); mark(2);
-    launch_cholesky(P, s); mark(3);
-    mark(5);  // (gn_finalize: fused into the Cholesky's back substitution; phase kept for the ABI list)
-    launch_lm_backsub(P, s); mark(4);
-    mark(6);  // (jv: the trailing workgroups of lm_backsub; phase kept for the ABI list)
-    mark(7);  // (the J*v reduction runs inside k_dogleg)
-    launch_dogleg(P, s); mark(8);
-    launch_eval_obs(P, 1, s); mark(9);
-    launch_eval_imu(P, 1, s); mark(10);
-    launch_eval_priors(P, 1, s);
-    evalHost(1, s); mark(11);  // host-evaluated factors at the candidate (counted with the priors)
-    launch_reduce(P, R_COST_CAND, s); mark(12);
-    launch_linearization_blocks(P, 1, s); mark(13);
-    launch_gradnorm(P, 1, s); mark(14);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    for (size_t i = 1; i < ev.size(); ++i) {
-      float t = 0.f;
-      HIPCHK(hipEventElapsedTime(&t, ev[i - 1], ev[i]));
-      ms[phaseOf[i]] += t;
-    }
-    for (auto e : ev) (void)hipEventDestroy(e);
   }
 
   ~okvisgpu_ctx() {
@@ -542,6 +512,7 @@ struct okvisgpu_ctx {
     L.patch(base);
     P.gL = P.lm_g;  // the landmark gradient is the accumulated J_l^T r
     HIPCHK(hipStreamSynchronize(stream));
+    decideRegime(0);  // (default options: the entry points that launch without a solve_begin)
     uploadDescriptor();
     ensureHostBuffers();
     haveProblem = true;
@@ -570,32 +541,7 @@ struct okvisgpu_ctx {
     d.min_relative_decrease = o.min_relative_decrease;
     d.min_lm_diagonal = o.min_lm_diagonal;
     d.max_lm_diagonal = o.max_lm_diagonal;
-    // Cholesky schedule (measured on MI355X, S50 windows, bench window-it/s, round 4 with the
-    // nested-dissection order (nd) below one window per CU: 64 windows: schedule 1 65.2k, 2 (nd)
-    // 72.2k; 128: 1 103.6k, 3 (nd) 107.9k, 2 (nd) 98.2k; 256: 1 159.7k, 3 (nd) 152.8k; 512: 1
-    // 186.5k, 3 (nd) 166.0k; gpurun_out r04g / r04h nd_probe; round 5, the pipelined two-team
-    // kernel (4), gpurun_out r05g: 64: 2 74.1k, 4 67.0k; 128: 3 110.1k, 4 105.7k; 256: 1 161.0k,
-    // 4 170.1k; 512: 1 186.7k, 4 178.7k; the split schedule with pipelined parts (5), r05s: 64: 2
-    // 73.9k, 3 70.4k, 5 73.7k; 128: 3 109.8k, 5 114.5k; 192: 4 133.6k, 3 127.3k, 5 120.7k; one S50
-    // window: 2 2,765, 5 2,336, 3 2,233, 4 1,858 it/s): below half a window per CU the
-    // tile-parallel launches spread each window over many CUs; at half a window per CU the split
-    // schedule with each part pipelined; up to one window per CU the pipelined kernel (its step is
-    // the factor plus one panel and one update); from there one persistent workgroup per window,
-    // two per CU. (A wave-specialised kernel and a persistent variant with the panel tiles in LDS were
-    // measured slower at every batch size and removed in round 4; a two-window pipelined
-    // workgroup, round 5, ran 166.8k against 199.4k at 2,048 windows and was removed.)
-    int sched = o.cholesky_schedule >= 1 && o.cholesky_schedule <= 5 ? o.cholesky_schedule : 0;
-    if (sched == 0)
-      sched = 2 * P.n_win < cuCount ? 2 : (2 * P.n_win <= cuCount && B.any_split ? 5 : (P.n_win <= cuCount ? 4 : 1));
-    if (sched == 3 && !B.any_split) sched = 1;  // (no window with a nested-dissection split)
-    if (sched == 5 && !B.any_split) sched = 4;
-    // the persistent kernel keeps the window's rhs / y in dynamic LDS next to its static tiles:
-    // a reduced dimension beyond what fits falls back to the tile-parallel launches
-    if (sched == 5 && !(pipeFits() && persistentFits())) sched = 3;
-    if (sched == 4 && !pipeFits()) sched = 1;
-    if ((sched == 1 || sched == 3) && !persistentFits()) sched = 2;
-    if (sched != P.chol_schedule) dropGraph();
-    P.chol_schedule = sched;
+    decideRegime(o.cholesky_schedule);  // (drops the captured graph when the Cholesky schedule changes)
     uploadDescriptor();
   }
 
@@ -697,122 +643,159 @@ struct okvisgpu_ctx {
   void launchInit(int evalMode) {
     evalAll(evalMode, stream);
     launch_reduce(P, R_COST_INIT, stream);
-    launch_linearization_blocks(P, 0, stream);
+    launch_lm_blocks(P, 0, stream);
+    launch_imu_hess(P, 0, stream);
+    launch_fgrad(P, 0, stream);
     launch_gradnorm(P, 0, stream);
-    if (lin_runs_prep(P)) launch_lm_prep(P, stream);  // (the first iteration's; later ones: k_lin_few)
+    if (regime.lin_prep) launch_lm_prep(P, stream);  // (the first iteration's; later ones: k_lin_few, runTimed)
     HIPCHK(hipGetLastError());
   }
 
-  // One iteration. Few windows (a latency chain of small launches): the gradient test of an
-  // iteration runs inside the next iteration's assembly launch (k_assemble_few; it reads nothing the
-  // assembly writes, and a window it ends is skipped from the Cholesky on), and the captured
-  // graph ends with one standalone test (graphTail), so that every graph launch leaves complete
-  // window states. The test is idempotent (the same state gives the same norms and decision), so
-  // the repeat at the start of the next graph launch is harmless.
-  bool fusedGradnorm() const { return fewWindows(P.n_win, P.cu_count); }
-  void launchIteration() {
-    if (!lin_runs_prep(P)) launch_lm_prep(P, stream);
-    if (fusedGradnorm()) launch_assemble_gradnorm_few(P, stream);
-    else launch_assemble(P, stream);
-    launch_cholesky(P, stream);
-    launch_gn_backsub(P, stream);  // (with the factors' J*v)
-    launch_dogleg(P, stream);
-    evalAll(1, stream);
-    launch_reduce(P, R_COST_CAND, stream);
-    launch_linearization_blocks(P, 1, stream);
-    if (!fusedGradnorm()) launch_gradnorm(P, 1, stream);
+  // ---- one trust-region iteration: a table of steps, walked by three executors -------------------
+  // A step is a launcher, the ABI phase its device time is booked to (kPhaseNames) and the lane it
+  // may run on: a step on a side lane is independent of the main-lane step before it and of the
+  // other side lane's (disjoint data: pose-pose vs. speed/bias blocks of S; observation / IMU, prior
+  // and edge / host-factor records; landmark groups vs. IMU Hessians), so a main-lane step and the
+  // side-lane steps after it are one fork / join group.
+  enum Lane { MAIN = 0, SIDE0 = 1, SIDE1 = 2 };
+  struct Step {
+    void (*launch)(okvisgpu_ctx& c, hipStream_t s);
+    int phase, lane;
+  };
+#define STEP(phase, lane, call) Step{[](okvisgpu_ctx& c, hipStream_t s) { call; }, phase, lane}
+  // The iteration of every batch but a few windows on one stream, and of every eager iteration (the
+  // ABI's phases and the four Summary sums are per kernel, so the timed iteration stays unfused also
+  // where the solve it reports on runs fewSteps(): the same device code on the same data in the same
+  // order per buffer, and runTimed() closes with the prep that fewSteps() expects: the same bits,
+  // also when eager and captured iterations alternate in one solve). Phases 1 zero_S, 5 gn_finalize, 6 jv and 7 reduce_jv no longer
+  // launch (S is cleared once per build; the others run inside cholesky, lm_backsub and dogleg): they
+  // stay in the ABI's list and report 0.
+  static const std::vector<Step>& unfusedSteps() {
+    static const std::vector<Step> t = {
+        STEP(0, MAIN, launch_lm_prep(c.P, s)),  // GN prep: only windows whose Z is stale
+        STEP(2, MAIN, launch_assemble_pp(c.P, s)),
+        STEP(2, SIDE0, launch_assemble_sb(c.P, s)),
+        STEP(3, MAIN, launch_cholesky(c.P, s)),    // (with the f-blocks' GN vectors)
+        STEP(4, MAIN, launch_lm_backsub(c.P, s)),  // (with the dogleg vectors and every J*v)
+        STEP(8, MAIN, launch_dogleg(c.P, s)),
+        STEP(9, MAIN, launch_eval_obs(c.P, 1, s)),  // candidate evaluation
+        STEP(10, SIDE0, launch_eval_imu(c.P, 1, s)),  // (with the priors and edges)
+        STEP(11, SIDE1, c.evalHost(1, s)),
+        STEP(12, MAIN, launch_reduce(c.P, R_COST_CAND, s)),
+        STEP(13, MAIN, launch_lm_blocks(c.P, 1, s)),  // linearisation at the accepted point
+        STEP(13, SIDE0, launch_imu_hess(c.P, 1, s)),
+        STEP(13, MAIN, launch_fgrad(c.P, 1, s)),
+        STEP(14, MAIN, launch_gradnorm(c.P, 1, s)),
+    };
+    return t;
   }
-  void graphTail(bool serial) {
-    if (serial && fusedGradnorm()) launch_gradnorm(P, 1, stream);
+  // Few windows on one stream (regime.fused_gradnorm; a latency chain of small launches): the
+  // independent kernels of a group as one launch, the GN prep inside the linearisation launch unless
+  // regime.lin_prep is off (then captureIterations() puts launch_lm_prep in front), and the
+  // gradient test of an iteration inside the next iteration's assembly launch (k_assemble_few; it
+  // reads nothing the assembly writes, and a window it ends is skipped from the Cholesky on).
+  // Invariant (prepPending()): with the prep inside the linearisation, this list starts from Z, L^-1
+  // and partial Schur blocks already formed for every window's current mu, so whatever ran before it
+  // (launchInit, the list itself, an eager iteration) must have ended with the prep of the windows
+  // whose step was not accepted: a mu raised by a failed Cholesky or an invalid step is otherwise
+  // assembled with operands of the old mu. The captured graph ends with one standalone test, so that every graph launch leaves complete window
+  // states; the test is idempotent (the same state gives the same norms and decision), so the
+  // repeat at the start of the next graph launch is harmless.
+  static const std::vector<Step>& fewSteps() {
+    static const std::vector<Step> t = {
+        STEP(2, MAIN, launch_assemble_gradnorm_few(c.P, s)),
+        STEP(3, MAIN, launch_cholesky(c.P, s)),
+        STEP(4, MAIN, launch_lm_backsub(c.P, s)),
+        STEP(8, MAIN, launch_dogleg(c.P, s)),
+        STEP(9, MAIN, launch_eval_few(c.P, 1, s)),
+        STEP(11, MAIN, c.evalHost(1, s)),
+        STEP(12, MAIN, launch_reduce(c.P, R_COST_CAND, s)),
+        STEP(13, MAIN, launch_lin_few(c.P, s)),
+        STEP(13, MAIN, launch_fgrad(c.P, 1, s)),
+    };
+    return t;
   }
+#undef STEP
 
-  // The captured iteration with the independent kernels of a phase on fork streams, so the graph
-  // runs them concurrently (the latency of a single window is a chain of small kernels); the data
-  // they touch is disjoint (eval: obs / IMU / prior records; linearisation: landmark groups / IMU
-  // Hessians; J*v: reprojection rows / factor rows; S tiles zeroed vs. landmark-group records;
-  // pose-pose vs. speed/bias blocks of S).
-  void launchIterationForked() {
-    size_t& ne = forkEvUsed;  // (distinct events for every fork / join of one capture)
-    auto ev = [&]() {
-      if (ne == forkEv.size()) {
+  // fewSteps() follows and will not start with the GN prep: what runs before it must end with one
+  bool prepPending() const { return regime.fused_gradnorm && regime.lin_prep; }
+
+  // Serial executor (one-stream capture): the lanes are ignored.
+  void runSerial(const std::vector<Step>& steps) {
+    for (const Step& st : steps) st.launch(*this, stream);
+  }
+  // Forked executor (capture with fork streams, so the graph runs a group's kernels concurrently):
+  // per group, the side lanes wait for an event of the main stream, the side-lane steps are
+  // captured, then the main-lane step, and the main stream waits for an event of each side lane.
+  // Every fork and join of one capture has its own event.
+  void runForked(const std::vector<Step>& steps) {
+    hipStream_t lane[3] = {stream, side[0], side[1]};
+    auto edge = [&](hipStream_t from, hipStream_t to) {
+      if (forkEvUsed == forkEv.size()) {
         hipEvent_t e;
         HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         forkEv.push_back(e);
       }
-      return forkEv[ne++];
-    };
-    auto fork = [&](hipStream_t to) {
-      hipEvent_t e = ev();
-      HIPCHK(hipEventRecord(e, stream));
+      hipEvent_t e = forkEv[forkEvUsed++];
+      HIPCHK(hipEventRecord(e, from));
       HIPCHK(hipStreamWaitEvent(to, e, 0));
     };
-    auto join = [&](hipStream_t from) {
-      hipEvent_t e = ev();
-      HIPCHK(hipEventRecord(e, from));
-      HIPCHK(hipStreamWaitEvent(stream, e, 0));
-    };
-    // Gauss-Newton system: the stale Z rebuilt (few windows after the first iteration), then the
-    // assembly kernels and the clearing of the tile entries they do not write, on four streams
-    // (disjoint entries of S)
-    launch_lm_prep(P, stream);
-    fork(side[0]);
-    launch_assemble_sb(P, side[0]);
-    launch_assemble_pp(P, stream);
-    join(side[0]);
-    launch_cholesky(P, stream);  // (with the f-blocks' GN vectors, formerly k_gn_finalize)
-    launch_lm_backsub(P, stream);  // (with the factors' J*v)
-    launch_dogleg(P, stream);
-    // candidate evaluation
-    fork(side[0]);
-    fork(side[1]);
-    launch_eval_imu(P, 1, side[0]);
-    launch_eval_priors(P, 1, side[1]);
-    evalHost(1, side[1]);
-    launch_eval_obs(P, 1, stream);
-    join(side[0]);
-    join(side[1]);
-    launch_reduce(P, R_COST_CAND, stream);
-    // linearisation at the accepted point
-    fork(side[0]);
-    launch_imu_hess(P, 1, side[0]);
-    launch_lm_blocks(P, 1, stream);
-    join(side[0]);
-    launch_fgrad(P, 1, stream);
-    launch_gradnorm(P, 1, stream);
+    for (size_t i = 0, j; i < steps.size(); i = j) {
+      for (j = i + 1; j < steps.size() && steps[j].lane != MAIN;) ++j;
+      for (size_t k = i + 1; k < j; ++k) edge(stream, lane[steps[k].lane]);
+      for (size_t k = i + 1; k < j; ++k) steps[k].launch(*this, lane[steps[k].lane]);
+      steps[i].launch(*this, stream);
+      for (size_t k = i + 1; k < j; ++k) edge(lane[steps[k].lane], stream);
+    }
+  }
+  // Eager executor (okvisgpu_profile_iteration and the verbose solve): the unfused steps on the
+  // context's stream with a HIP event after each; ms[phase] += the step's device time. Where the
+  // captured graph is fewSteps() the iteration closes with the GN prep (the first step again, phase
+  // 0), as k_lin_few does there: captured iterations may follow.
+  void runTimed(double* ms) {
+    std::vector<Step> steps = unfusedSteps();
+    if (prepPending()) steps.push_back(steps.front());
+    std::vector<hipEvent_t> ev(steps.size() + 1);
+    for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(ev[0], stream));
+    for (size_t i = 0; i < steps.size(); ++i) {
+      steps[i].launch(*this, stream);
+      HIPCHK(hipEventRecord(ev[i + 1], stream));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    for (size_t i = 0; i < steps.size(); ++i) {
+      float t = 0.f;
+      HIPCHK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+      ms[steps[i].phase] += t;
+    }
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
   }
 
+  // k iterations captured as one graph, as the regime lays them out
+  hipGraphExec_t captureIterations(int k) {
+    hipGraph_t g;
+    hipGraphExec_t exec = nullptr;
+    HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+    forkEvUsed = 0;
+    for (int i = 0; i < k; ++i) {
+      if (regime.fused_gradnorm && !prepPending()) launch_lm_prep(P, stream);
+      if (regime.fused_gradnorm) runSerial(fewSteps());
+      else if (regime.serial_graph) runSerial(unfusedSteps());
+      else runForked(unfusedSteps());
+    }
+    if (regime.fused_gradnorm) launch_gradnorm(P, 1, stream);
+    HIPCHK(hipStreamEndCapture(stream, &g));
+    HIPCHK(hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
+    HIPCHK(hipGraphDestroy(g));
+    return exec;
+  }
   void ensureGraph() {
     if (iterGraph) return;
-    hipGraph_t g;
-    HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    // Few windows: one stream (a cross-stream edge of the graph costs ~10 us, more than the
-    // overlap of a single window's small kernels gains: S50 1488 -> 1614 it/s); a full batch
-    // keeps the fork streams (2,048 S50 windows: 135.7k -> 138.5k window-it/s). Env override
-    // OKVISGPU_SERIAL_GRAPH=0|1 (measurements).
-    const char* ser = std::getenv("OKVISGPU_SERIAL_GRAPH");
-    const bool serial = ser && (ser[0] == '0' || ser[0] == '1') ? ser[0] == '1' : P.n_win < cuCount;
-    forkEvUsed = 0;
-    if (serial) launchIteration();
-    else launchIterationForked();
-    graphTail(serial);
-    HIPCHK(hipStreamEndCapture(stream, &g));
-    HIPCHK(hipGraphInstantiate(&iterGraph, g, nullptr, nullptr, 0));
-    HIPCHK(hipGraphDestroy(g));
-    // Env override OKVISGPU_GRAPH_ITERS=<K> (measurements; 1 = single-iteration graph only).
-    const char* gi = std::getenv("OKVISGPU_GRAPH_ITERS");
-    const int K = gi && *gi ? std::max(1, std::min(std::atoi(gi), 64)) : kGraphIters;
-    if (K > 1) {
-      HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-      forkEvUsed = 0;
-      for (int k = 0; k < K; ++k) {
-        if (serial) launchIteration();
-        else launchIterationForked();
-      }
-      graphTail(serial);
-      HIPCHK(hipStreamEndCapture(stream, &g));
-      HIPCHK(hipGraphInstantiate(&iterGraphK, g, nullptr, nullptr, 0));
-      HIPCHK(hipGraphDestroy(g));
-      graphIters = K;
+    iterGraph = captureIterations(1);
+    if (regime.graph_iters > 1) {
+      iterGraphK = captureIterations(regime.graph_iters);
+      graphIters = regime.graph_iters;
     }
   }
 };
@@ -906,6 +889,8 @@ int okvisgpu_ctx_create(int32_t device, okvisgpu_ctx** out) {
                      OKVISGPU_ERR_DEVICE};
     c->cuCount = prop.multiProcessorCount;
     c->ldsPerBlock = prop.sharedMemPerBlock;
+    c->persistentLds = cholesky_persistent_lds();
+    c->pipeLds = cholesky_pipe_lds();
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (hipStream_t& q : c->side) HIPCHK(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
     return (int)OKVISGPU_OK;
@@ -996,8 +981,6 @@ int okvisgpu_solve_begin(okvisgpu_ctx* c, const okvisgpu_options* o) {
     if (c->structureDirty) c->build();  // freeze / unfreeze changed the free set
     c->setOptions(*o);
     c->dropGraph();  // options are baked into the captured kernel arguments
-    c->P.lin_prep = -1;  // the GN prep's placement: decided once, used by launchInit and the capture
-    c->P.lin_prep = lin_runs_prep(c->P) ? 1 : 0;
     c->uploadParams();
     c->resetStates(1e-8);
     c->ensureS(c->stream);
@@ -1044,7 +1027,7 @@ int okvisgpu_solve_end(okvisgpu_ctx* c, okvisgpu_summary* sums) {
       bool allDone = true;
       for (auto& s : st) allDone = allDone && s.done;
       if (allDone) break;
-      HIPCHK(hipGraphLaunch(c->iterGraph, c->stream));
+      c->launchIterations(1);
       ++c->replays;
       st = c->readStates();
     }
@@ -1089,8 +1072,8 @@ int okvisgpu_solve(okvisgpu_ctx* c, const okvisgpu_options* o, okvisgpu_summary*
         continue;
       }
       iterStart = nowS();
-      if (o->verbose) c->profiledIteration(c->phaseMs);
-      else HIPCHK(hipGraphLaunch(c->iterGraph, c->stream));
+      if (o->verbose) c->runTimed(c->phaseMs);
+      else c->launchIterations(1);
       ++c->replays;
       st = c->readStates();
     }
@@ -1111,7 +1094,7 @@ int okvisgpu_profile_iteration(okvisgpu_ctx* c, double* ms) {
   if (!c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "profile_iteration needs solve_begin");
   return guarded(c, [&]() {
     for (int i = 0; i < OKVISGPU_N_PHASES; ++i) ms[i] = 0.0;
-    c->profiledIteration(ms);
+    c->runTimed(ms);
     c->replays += 1;
     return (int)OKVISGPU_OK;
   });
@@ -1379,7 +1362,8 @@ int okvisgpu_linearize_reduce(okvisgpu_ctx* c, int32_t window, int32_t jacobi_sc
     c->setOptions(o);
     c->resetStates(mu);
     c->launchInit(2);
-    launch_gn_reduce(c->P, c->stream);
+    launch_lm_prep(c->P, c->stream);
+    launch_assemble(c->P, c->stream);
     HIPCHK(hipGetLastError());
     auto st = c->readStates();
     // exported in the natural order (pose i, speed/bias i, ..., extrinsics), whatever order the

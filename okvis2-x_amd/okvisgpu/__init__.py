@@ -209,6 +209,7 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_graph_load", "okvisgpu_graph_problem", "okvisgpu_graph_ids", "okvisgpu_graph_destroy",
     "okvisgpu_graph_save", "okvisgpu_get_stats", "okvisgpu_synth_true_extrinsics", "okvisgpu_imu_append",
     "okvisgpu_eval_host", "okvisgpu_plan_window", "okvisgpu_loss_evaluate", "okvisgpu_plan_digest",
+    "okvisgpu_launch_regime",
 ]
 N_PHASES = 15
 
@@ -270,6 +271,7 @@ def lib():
         L.okvisgpu_plan_window.argtypes = [C.POINTER(Problem), C.c_int32, _lp, C.POINTER(C.c_uint8), _ip, _ip]
         L.okvisgpu_plan_digest.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, _lp, C.c_int32, _ip, C.c_char_p,
                                            _ip, _lp, C.POINTER(C.c_uint64)]
+        L.okvisgpu_launch_regime.argtypes = [C.c_int32] * 9 + [_ip]
         L.okvisgpu_imu_append.argtypes = [C.c_void_p, C.POINTER(ImuAppendBatch), _ip]
         L.okvisgpu_twopose_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _dp, _dp]
         L.okvisgpu_loss_evaluate.argtypes = [C.POINTER(Loss), C.c_double, _dp]
@@ -326,6 +328,22 @@ def plan_digest(problems, cu_count):
     entries = [[names.raw[32 * i:32 * i + 32].split(b"\0")[0].decode(), int(region[i]), int(nbytes[i]),
                 f"{hashes[i]:016x}" if region[i] == 0 else None] for i in range(cap)]
     return {"totals": {k: int(v) for k, v in zip(PLAN_DIGEST_TOTALS, totals)}, "entries": entries}
+
+
+LAUNCH_REGIME = ("few", "many", "serial_graph", "lin_prep", "fused_gradnorm", "graph_iters", "chol_schedule")
+
+
+def launch_regime(n_windows, cu_count, any_split=False, persistent_fits=True, pipe_fits=True, schedule=0,
+                  serial_graph=-1, lin_prep=-1, graph_iters=-1):
+    """okvisgpu_launch_regime (host only): what the batch size decides about a solve's launches; the
+    last three arguments are the parsed measurement overrides (-1: not set)."""
+    out = (C.c_int32 * 7)()
+    rc = lib().okvisgpu_launch_regime(int(n_windows), int(cu_count), int(any_split), int(persistent_fits),
+                                      int(pipe_fits), int(schedule), int(serial_graph), int(lin_prep),
+                                      int(graph_iters), out)
+    if rc != 0:
+        raise RuntimeError(f"okvisgpu_launch_regime failed ({rc})")
+    return dict(zip(LAUNCH_REGIME, (int(v) for v in out)))
 
 
 def default_options(**kw) -> Options:

@@ -229,7 +229,7 @@ def test_batched_windows_match_single(og, gpu_ctx):
 def test_window_alone_vs_large_batch(og, gpu_ctx, parity, n_batch):
     """A window's operation order depends on the batch only through the batch size against the
     device's CU count (runtime.cpp: the nested-dissection state order below one window per CU;
-    device_problem.hpp fewWindows: 1,024-thread per-window reductions and fused launches at or
+    plan.hpp fewWindows: 1,024-thread per-window reductions and fused launches at or
     below a quarter window per CU). On MI355X (256 CUs) a window alone runs with both, in a batch of
     100 with the order but not the reductions, in a batch of 300 with neither. Bitwise equality
     holds inside one regime (test_batched_windows_match_single); across regimes the solves agree to
@@ -306,7 +306,7 @@ def test_solve_is_deterministic(og, gpu_ctx):
 
 def test_forked_and_serial_graphs_agree(og, gpu_ctx, monkeypatch):
     """The captured iteration with fork streams (batches of at least one window per CU) and the
-    single-stream one (fewer windows; runtime.cpp ensureGraph) run the same kernels on disjoint
+    single-stream one (fewer windows; plan.cpp launchRegime, runtime.cpp runForked / runSerial) run the same kernels on disjoint
     data in a fixed order per buffer: bitwise-equal solves, also with mu retries (GN prep)."""
     ws = [_window(og, seed=s) for s in (41, 42, 43)]
     opts = og.default_options(max_num_iterations=6, function_tolerance=0.0, gradient_tolerance=0.0,
@@ -349,6 +349,34 @@ def test_graph_iterations_and_prep_placement_agree(og, gpu_ctx, monkeypatch):
             assert r[0][k]["num_iterations"] == res[0][0][k]["num_iterations"] == 7
             assert np.array_equal(r[1][k], res[0][1][k])
             assert np.array_equal(r[2][k], res[0][2][k])
+
+
+@pytest.mark.parametrize("shape,n_win,serial", [((6, 150, 1000), 3, "0"), ((3, 40, 200), 65, None)],
+                         ids=["forked3", "serial65"])
+def test_eager_and_captured_iterations_agree(og, gpu_ctx, monkeypatch, shape, n_win, serial):
+    """The eager iteration of a verbose solve (runtime.cpp runTimed: the unfused step table on one
+    stream, an event after each step) against the captured one of a plain solve of the same windows:
+    three windows on the forked graph (OKVISGPU_SERIAL_GRAPH=0), and 65 windows, which on 256 CUs is
+    the one-stream graph of the unfused table. The same kernels in the same order per buffer:
+    bitwise-equal solves."""
+    if serial is None:
+        monkeypatch.delenv("OKVISGPU_SERIAL_GRAPH", raising=False)
+    else:
+        monkeypatch.setenv("OKVISGPU_SERIAL_GRAPH", serial)
+    ws = [og.SynthWindow(*shape, seed=900 + k) for k in range(n_win)]
+    res = []
+    for verbose in (1, 0):
+        for w in ws:
+            w.reset()
+        gpu_ctx.set_problems([w.problem for w in ws])
+        s = gpu_ctx.solve(og.default_options(max_num_iterations=6, function_tolerance=0.0, gradient_tolerance=0.0,
+                                             parameter_tolerance=0.0, verbose=verbose), n_win)
+        res.append((s, [w.poses().copy() for w in ws], [w.landmarks().copy() for w in ws]))
+    for k in range(n_win):
+        assert res[0][0][k]["final_cost"] == res[1][0][k]["final_cost"]
+        assert res[0][0][k]["num_iterations"] == res[1][0][k]["num_iterations"]
+        assert np.array_equal(res[0][1][k], res[1][1][k])
+        assert np.array_equal(res[0][2][k], res[1][2][k])
 
 
 def _close(sg, so, rel=1e-7):
@@ -613,6 +641,42 @@ def _window_with_degenerate_state(og, seed, j=25):
     P.host_fn = og.host_evaluate(lambda h, prm: (np.array([0.1]), [np.zeros((1, 7)), np.zeros((1, 9))]), [[7, 9]])
     P.bind()
     return P
+
+
+def test_eager_and_captured_iterations_alternate_with_mu_retries(og, gpu_ctx):
+    """okvisgpu_profile_iteration (eager) and solve_iterate (the captured few-window graph, which
+    does not start with the GN prep) alternating in one solve of a window that takes mu retries in
+    every iteration: an eager iteration must leave Z, L^-1 and the partial Schur blocks formed for
+    the raised mu, as the captured one does (k_lin_few's prep). The extra state's columns of J are
+    zero, so its pivot is min_lm_diagonal * mu: with min_lm_diagonal = 1e-318 that underflows to 0
+    below mu = 1e-5 (the smallest FP64 subnormal is 4.9e-324), the factorisation fails at mu = 1e-8,
+    1e-7, 1e-6 and succeeds at 1e-5; after an accepted step mu drops again (Ceres: mu / 5) and the
+    next iteration retries. Eager passes at the even, then at the odd positions, so that a retry
+    falls before a captured pass either way: the bits of the solve without profiling."""
+    opts = og.default_options(max_num_iterations=4, function_tolerance=0.0, gradient_tolerance=0.0,
+                              parameter_tolerance=0.0, min_lm_diagonal=1e-318)
+    P = _window_with_degenerate_state(og, seed=71)
+    snap = P.snapshot()
+    res = []
+    for eager_at in (None, 0, 1):
+        P.restore(snap)
+        gpu_ctx.set_problems([P.struct])
+        gpu_ctx.solve_begin(opts)
+        for k in range(12):
+            if eager_at is not None and k % 2 == eager_at:
+                gpu_ctx.profile_iteration()
+            else:
+                gpu_ctx.solve_iterate(1)
+        res.append((gpu_ctx.solve_end(1)[0], P.poses.copy(), P.landmarks.copy()))
+    s0 = res[0][0]
+    print("mu retries:", {k: s0[k] for k in ("num_iterations", "num_successful_steps", "num_unsuccessful_steps",
+                                             "final_mu", "termination", "final_cost")})
+    assert s0["num_iterations"] == 4 and s0["num_successful_steps"] >= 3, s0
+    assert 1e-6 <= s0["final_mu"] <= 1e-4, s0  # (retried up from 1e-8 to where the pivot survives, then / 5)
+    for s, x, l in res[1:]:
+        assert s["final_cost"] == s0["final_cost"] and s["num_iterations"] == s0["num_iterations"], (s, s0)
+        assert s["final_mu"] == s0["final_mu"], (s, s0)
+        assert np.array_equal(x, res[0][1]) and np.array_equal(l, res[0][2])
 
 
 def test_cholesky_failure_path_all_schedules(og, oracle, gpu_ctx):
