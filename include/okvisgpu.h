@@ -441,6 +441,39 @@ typedef struct okvisgpu_imu_append_batch {
 } okvisgpu_imu_append_batch;
 int okvisgpu_imu_append(okvisgpu_ctx* ctx, const okvisgpu_imu_append_batch* batch, int32_t* steps);
 
+/* ---------------------------------------------------------------- post-solve landmark pass
+ * (An addition to ABI 6: a new entry point and a new struct; no existing struct or call changes, so
+ * OKVISGPU_ABI_VERSION stays 6 and a caller built against the earlier header keeps working.)
+ * ViGraph::updateLandmarks (ViGraph.cpp:1762-1841) and ViGraph::areLandmarksInFrontOfCameras
+ * (:1621-1642) for every window of the batch on the GPU, on the parameter values okvisgpu_get_params
+ * would return now (after a solve the solved ones, after okvisgpu_set_problems / _update_params the
+ * uploaded ones; T_SC is the camera's pose-kind block, so a variable extrinsics block counts with its
+ * solved value). Per landmark, over its observations in (pose, camera) order: the unit ray dir_W from
+ * the camera to the landmark (reversed when the landmark lies behind the camera) and the norm of the
+ * weighted reprojection residual without loss (what okvisgpu_eval_reprojection returns);
+ * observations with a norm above 2.5 are skipped. quality = the norm of the per-axis root sums of
+ * squared deviations of the kept rays from their mean (0 without a kept ray); quality > 0.04 makes
+ * the landmark initialised; otherwise, if an observation (kept or not) saw it closer than 0.1 m in
+ * depth, it is re-placed on the ray of the kept observation with the smallest residual, at its
+ * distance (at least 0.1 m) in front of that camera, as [x y z 1]: in both device parameter sets and
+ * in the caller's `landmarks` array. Nothing else in the caller's arrays changes. Indices are the
+ * caller's (landmark l of okvisgpu_problem.landmarks, observation o of obs_*). A landmark without
+ * observations: quality 0, not initialised, untouched. Constant landmarks are treated like any other.
+ * in_front is evaluated on the values at entry, before any landmark is re-placed. */
+typedef struct okvisgpu_landmark_update {   /* one per window; arrays caller-owned, any may be NULL */
+  double*  quality;                 /* [n_landmarks]   ViGraph::Landmark::quality                    */
+  uint8_t* initialised;             /* [n_landmarks]   hPoint->setInitialized()                      */
+  uint8_t* reset;                   /* [n_landmarks]   1 = the estimate was replaced (best-ray reset) */
+  double*  obs_error;               /* [n_observations] |weighted reprojection residual|, no loss    */
+  int32_t  n_initialised, n_reset;  /* out                                                           */
+  int32_t  in_front;                /* out: ViGraph::areLandmarksInFrontOfCameras() on the entry values */
+  int32_t  reserved;
+} okvisgpu_landmark_update;
+/* updates: [n_windows of the last okvisgpu_set_problems]. OKVISGPU_ERR_INVALID_ARGUMENT for a NULL
+ * ctx or updates and between okvisgpu_solve_begin and _solve_end; OKVISGPU_ERR_NO_PROBLEM when no
+ * problem is set. */
+int okvisgpu_update_landmarks(okvisgpu_ctx* ctx, okvisgpu_landmark_update* updates);
+
 /* ---------------------------------------------------------------- okvis Component graphs
  * Component::load (okvis_ceres/src/Component.cpp:50-383) as an okvisgpu_problem: states (pose and
  * speed/bias blocks, ordered by state id), landmarks (ordered by id), one extrinsics block per camera,

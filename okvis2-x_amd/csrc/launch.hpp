@@ -63,4 +63,13 @@ void launch_select_current(const DevProblem& P, hipStream_t s);  // set 1 -> set
 // pose-graph edges (kernels_twopose.hip): TwoPoseStandardGraphError::compute, one wavefront per edge
 void launch_twopose_compute(const TwoPoseDev& T, hipStream_t s);
 
+
+// post-solve landmark pass (kernels_landmarks.hip): ViGraph::updateLandmarks on parameter set 0 (run
+// launch_select_current first), one lane per landmark. Outputs in device order: quality [n_lm],
+// flags [n_lm] (kLmInitialised | kLmReset | kLmNotInFront), obs_err [n_obs]; dirs [n_obs][3] is
+// scratch. Re-placed landmarks are written to both parameter sets.
+constexpr uint8_t kLmInitialised = 1, kLmReset = 2, kLmNotInFront = 4;
+void launch_update_landmarks(const DevProblem& P, double* quality, uint8_t* flags, double* obs_err, double* dirs,
+                             hipStream_t s);
+
 }  // namespace okg

@@ -209,6 +209,10 @@ struct okvisgpu_ctx {
   int hostBufFactors = 0;
   std::vector<uint8_t> hostFail;
   HostWorkers hostWorkers;
+  // okvisgpu_update_landmarks' device outputs (quality | kept rays | observation errors | flags):
+  // owned by the context, outside the arena table, allocated on first use and grown as needed
+  void* lmScratch = nullptr;
+  size_t lmScratchBytes = 0;
 
   void fillSummaries(const std::vector<WinState>& st, okvisgpu_summary* sums) {
     if (!sums) return;
@@ -266,6 +270,7 @@ struct okvisgpu_ctx {
     if (hostStage) (void)hipHostFree(hostStage);
     if (hostIn) (void)hipHostFree(hostIn);
     if (hostOut) (void)hipHostFree(hostOut);
+    if (lmScratch) (void)hipFree(lmScratch);
     for (hipEvent_t e : forkEv) (void)hipEventDestroy(e);
     for (hipStream_t q : side)
       if (q) (void)hipStreamDestroy(q);
@@ -630,6 +635,74 @@ struct okvisgpu_ctx {
       for (int k = 0; k < p->n_landmarks; ++k) std::memcpy(&p->landmarks[4 * (size_t)perm[k]], l + 4 * (size_t)k, 32);
       if (p->imu_state && p->n_imu)
         std::memcpy(p->imu_state, imu + (size_t)B.imu_base[w] * kImuState, sizeof(double) * kImuState * p->n_imu);
+    });
+  }
+
+  // ViGraph::updateLandmarks on the current parameter values (okvisgpu_update_landmarks): every
+  // window's current set is gathered into set 0 as downloadParams does (before the first solve
+  // WinState is the build's zeroed scratch: xcur = 0, set 0 holds the uploaded values), one kernel
+  // over the batch's landmarks, one copy per output into pinned memory, and a threaded scatter into
+  // the caller's order (landmarks through lm_perm, observations through obs_orig). Of the caller's
+  // problem arrays only the re-placed landmarks are written.
+  void updateLandmarks(okvisgpu_landmark_update* U) {
+    for (int w = 0; w < B.n_win; ++w) {
+      U[w].n_initialised = U[w].n_reset = 0;
+      U[w].in_front = 1;
+      U[w].reserved = 0;
+    }
+    const size_t nl = (size_t)P.n_lm, no = (size_t)P.n_obs;
+    if (nl == 0) return;  // nothing to launch
+    bool wantErr = false;
+    for (int w = 0; w < B.n_win; ++w) wantErr = wantErr || U[w].obs_error != nullptr;
+    // device: quality [nl] | dirs [no][3] | err [no] | flags [nl]; host: quality [nl] | lm [nl][4] | err [no] | flags [nl]
+    const size_t need = 8 * (nl + 4 * std::max<size_t>(no, 1)) + nl;
+    if (need > lmScratchBytes) {
+      if (lmScratch) HIPCHK(hipFree(lmScratch));
+      lmScratch = nullptr;
+      lmScratchBytes = 0;
+      HIPCHK(hipMalloc(&lmScratch, need));
+      lmScratchBytes = need;
+    }
+    double* dQ = static_cast<double*>(lmScratch);
+    double *dDirs = dQ + nl, *dErr = dDirs + 3 * no;
+    uint8_t* dFlags = reinterpret_cast<uint8_t*>(dErr + std::max<size_t>(no, 1));
+    double* hQ = reinterpret_cast<double*>(paramStage(8 * (nl + 4 * nl + no) + nl));
+    double *hLm = hQ + nl, *hErr = hLm + 4 * nl;
+    uint8_t* hFlags = reinterpret_cast<uint8_t*>(hErr + no);
+    launch_select_current(P, stream);
+    launch_update_landmarks(P, dQ, dFlags, dErr, dDirs, stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hQ, dQ, nl * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(hLm, P.lm[0], 4 * nl * 8, hipMemcpyDeviceToHost, stream));
+    if (wantErr && no) HIPCHK(hipMemcpyAsync(hErr, dErr, no * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(hFlags, dFlags, nl, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    forWindows(B.n_win, [&](int w) {
+      const okvisgpu_problem* p = probs[w];
+      okvisgpu_landmark_update& u = U[w];
+      const size_t lb = (size_t)B.lm_base[w];
+      const int* perm = &B.lm_perm[lb];
+      int nInit = 0, nReset = 0, front = 1;
+      for (int k = 0; k < p->n_landmarks; ++k) {
+        const int l = perm[k];
+        const uint8_t f = hFlags[lb + k];
+        if (u.quality) u.quality[l] = hQ[lb + k];
+        if (u.initialised) u.initialised[l] = (f & kLmInitialised) ? 1 : 0;
+        if (u.reset) u.reset[l] = (f & kLmReset) ? 1 : 0;
+        nInit += (f & kLmInitialised) ? 1 : 0;
+        if (f & kLmNotInFront) front = 0;
+        if (f & kLmReset) {
+          ++nReset;
+          std::memcpy(&p->landmarks[4 * (size_t)l], hLm + 4 * (lb + k), 32);
+        }
+      }
+      u.n_initialised = nInit;
+      u.n_reset = nReset;
+      u.in_front = front;
+      if (u.obs_error) {
+        const size_t ob = (size_t)B.obs_base[w];
+        for (int k = 0; k < p->n_observations; ++k) u.obs_error[B.obs_orig[ob + k]] = hErr[ob + k];
+      }
     });
   }
 
@@ -1562,6 +1635,17 @@ int okvisgpu_imu_append(okvisgpu_ctx* c, const okvisgpu_imu_append_batch* A, int
         const bool covered = s1 > s0 && A->sample_t_ns[s1 - 1] >= A->t1_new_ns[i];
         steps[i] = covered ? (int32_t)A->state[(size_t)i * kImuState + 291] : -1;
       }
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_update_landmarks(okvisgpu_ctx* c, okvisgpu_landmark_update* updates) {
+  if (!c || !updates) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "update_landmarks: bad arguments");
+  if (!c->haveProblem) return fail(c, OKVISGPU_ERR_NO_PROBLEM, "no problem set");
+  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "update_landmarks: call after solve_end");
+  return guarded(c, [&]() {
+    HIPCHK(hipSetDevice(c->device));
+    c->updateLandmarks(updates);
     return (int)OKVISGPU_OK;
   });
 }

@@ -195,6 +195,13 @@ class TwoPoseEdges(C.Structure):
                 ("obs_camera", _ip), ("obs_keypoint", _dp), ("obs_sqrt_info", _dp), ("obs_cauchy", _up)]
 
 
+class LandmarkUpdate(C.Structure):
+    """okvisgpu_landmark_update: one window's outputs of okvisgpu_update_landmarks."""
+    _fields_ = [("quality", _dp), ("initialised", _up), ("reset", _up), ("obs_error", _dp),
+                ("n_initialised", C.c_int32), ("n_reset", C.c_int32), ("in_front", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # Exported symbols of include/okvisgpu.h (checked by tests/test_abi.py).
 EXPORTED_SYMBOLS = [
     "okvisgpu_abi_version", "okvisgpu_default_options", "okvisgpu_device_count", "okvisgpu_ctx_create",
@@ -209,7 +216,7 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_graph_load", "okvisgpu_graph_problem", "okvisgpu_graph_ids", "okvisgpu_graph_destroy",
     "okvisgpu_graph_save", "okvisgpu_get_stats", "okvisgpu_synth_true_extrinsics", "okvisgpu_imu_append",
     "okvisgpu_eval_host", "okvisgpu_plan_window", "okvisgpu_loss_evaluate", "okvisgpu_plan_digest",
-    "okvisgpu_launch_regime",
+    "okvisgpu_launch_regime", "okvisgpu_update_landmarks",
 ]
 N_PHASES = 15
 
@@ -275,6 +282,7 @@ def lib():
         L.okvisgpu_imu_append.argtypes = [C.c_void_p, C.POINTER(ImuAppendBatch), _ip]
         L.okvisgpu_twopose_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _dp, _dp]
         L.okvisgpu_loss_evaluate.argtypes = [C.POINTER(Loss), C.c_double, _dp]
+        L.okvisgpu_update_landmarks.argtypes = [C.c_void_p, C.POINTER(LandmarkUpdate)]
         _lib = L
     return _lib
 
@@ -725,6 +733,26 @@ class Context:
         self._check(lib().okvisgpu_twopose_compute(self.h, C.byref(edges.struct), dptr(out["delta_x"]),
                                                    dptr(out["sqrt_info"]), dptr(out["lin_point"]), dptr(out["H00"]),
                                                    dptr(out["b0"])), "okvisgpu_twopose_compute")
+        return out
+
+    def update_landmarks(self, n_windows: Optional[int] = None):
+        """okvisgpu_update_landmarks (ViGraph::updateLandmarks on the current device values): one dict
+        per window with quality [n_landmarks], initialised / reset [n_landmarks] (bool), obs_error
+        [n_observations], n_initialised, n_reset and in_front (bool), in the caller's indices. A reset
+        landmark is re-placed on the device and in the window's `landmarks` array."""
+        n = self._n_windows(n_windows)
+        ups = (LandmarkUpdate * n)()
+        out = []
+        for u, p in zip(ups, self._keep[1]):
+            d = {"quality": np.zeros(p.n_landmarks), "initialised": np.zeros(p.n_landmarks, dtype=np.uint8),
+                 "reset": np.zeros(p.n_landmarks, dtype=np.uint8), "obs_error": np.zeros(p.n_observations)}
+            u.quality, u.obs_error = dptr(d["quality"]), dptr(d["obs_error"])
+            u.initialised, u.reset = d["initialised"].ctypes.data_as(_up), d["reset"].ctypes.data_as(_up)
+            out.append(d)
+        self._check(lib().okvisgpu_update_landmarks(self.h, ups), "okvisgpu_update_landmarks")
+        for u, d in zip(ups, out):
+            d["initialised"], d["reset"] = d["initialised"].astype(bool), d["reset"].astype(bool)
+            d["n_initialised"], d["n_reset"], d["in_front"] = int(u.n_initialised), int(u.n_reset), bool(u.in_front)
         return out
 
     def close(self):
