@@ -474,6 +474,33 @@ typedef struct okvisgpu_landmark_update {   /* one per window; arrays caller-own
  * problem is set. */
 int okvisgpu_update_landmarks(okvisgpu_ctx* ctx, okvisgpu_landmark_update* updates);
 
+/* ---------------------------------------------------------------- co-observation counts
+ * (An addition to ABI 6 like the landmark pass: a new entry point and a new struct.)
+ * ViGraph::computeCovisibilities (ViGraph.cpp:727-785) for every window of the batch on the GPU, in
+ * the caller's pose and landmark indices. A landmark adds 1 to counts[i][j] when it is not excluded
+ * and has at least one observation in pose i and at least one in pose j, i != j; two cameras of one
+ * frame count once. Every observation counts, whatever its residual, its loss flag or the landmark's
+ * constant flag; extrinsics blocks are not states and never appear. A landmark observed from a single
+ * pose makes that pose visible and adds to its n_observed, but adds no pair (visibleFrames_ is filled
+ * before the pair loop, :740-743). The result depends only on the structure given to the last
+ * okvisgpu_set_problems and on landmark_excluded, not on parameter values; nothing in the caller's
+ * problem arrays or on the device's parameter sets changes. A window without landmarks or
+ * observations gives all zeros and any = 0. */
+typedef struct okvisgpu_covisibility {   /* one per window; arrays caller-owned, any may be NULL */
+  const uint8_t* landmark_excluded; /* in  [n_landmarks] 1 = leave out (classification 10 / 11, ViGraph.cpp:735); NULL = none */
+  int32_t* counts;                  /* out [n_poses][n_poses] row-major, symmetric, zero diagonal:
+                                           counts[i][j] = ViGraph::covisibilities(i, j)              */
+  int32_t* n_observed;              /* out [n_poses] included landmarks the state observes          */
+  uint8_t* visible;                 /* out [n_poses] state is in visibleFrames_ (n_observed > 0)     */
+  int32_t  n_pairs;                 /* out: unordered pairs i<j with counts > 0                      */
+  int32_t  n_visible;               /* out                                                           */
+  int32_t  any;                     /* out: computeCovisibilities' return value (n_pairs > 0)        */
+  int32_t  path;                    /* out: 0 = window-in-LDS kernel, 1 = tiled kernel (informational) */
+} okvisgpu_covisibility;
+/* out: [n_windows of the last okvisgpu_set_problems]. OKVISGPU_ERR_INVALID_ARGUMENT for a NULL ctx or
+ * out and between okvisgpu_solve_begin and _solve_end; OKVISGPU_ERR_NO_PROBLEM when no problem is set. */
+int okvisgpu_covisibilities(okvisgpu_ctx* ctx, okvisgpu_covisibility* out);
+
 /* ---------------------------------------------------------------- okvis Component graphs
  * Component::load (okvis_ceres/src/Component.cpp:50-383) as an okvisgpu_problem: states (pose and
  * speed/bias blocks, ordered by state id), landmarks (ordered by id), one extrinsics block per camera,

@@ -72,4 +72,38 @@ constexpr uint8_t kLmInitialised = 1, kLmReset = 2, kLmNotInFront = 4;
 void launch_update_landmarks(const DevProblem& P, double* quality, uint8_t* flags, double* obs_err, double* dirs,
                              hipStream_t s);
 
+// co-observation counts (kernels_covis.hip): ViGraph::computeCovisibilities as a Gram product of the
+// window's 0/1 visibility matrix, counts[i][j] = popcount(v_i & v_j) on bit-vectors over the landmarks.
+// One record per window that has states, landmarks and observations (the others are all zero and never
+// reach the device); offsets are in elements of the batch-wide arrays.
+struct CovisWin {
+  int32_t lm_begin, n_lm;       // internal landmarks [lm_begin, lm_begin + n_lm)
+  int32_t pose_begin, n_state;  // states = global poses [pose_begin, pose_begin + n_state): extrinsics blocks excluded
+  int32_t word_begin, n_words;  // first 64-landmark word among all records' words; ceil(n_lm / 64)
+  int32_t state_off, pad_;      // offset into n_observed
+  int64_t bits_off;             // offset into bits, [n_state][n_words] state-major
+  int64_t counts_off;           // offset into counts, [n_state][n_state] row-major
+};
+// The constant between the two count kernels: a window whose bitset, at its padded row stride
+// covisRowStride(n_words), fits this many bytes of LDS is counted by one workgroup that holds all of it
+// (path 0); a larger one by (state tile x state tile) workgroups streaming word chunks (path 1).
+// 64 KiB of the CU's 160 KiB keeps two workgroups resident.
+constexpr size_t kCovisLdsBudget = 64 * 1024;
+constexpr int kCovisTile = 32;   // path 1: states per tile side
+constexpr int kCovisChunk = 32;  // path 1: words per chunk
+// LDS row stride in 64-bit words: odd, so the rows j, j + 1, ... a half-wave reads lie on distinct banks
+constexpr int covisRowStride(int n_words) { return n_words | 1; }
+constexpr size_t covisLdsBytes(int n_state, int n_words) { return 8 * (size_t)n_state * (size_t)covisRowStride(n_words); }
+constexpr bool covisFitsLds(int n_state, int n_words) { return covisLdsBytes(n_state, n_words) <= kCovisLdsBudget; }
+// bits: one wavefront per word; word_rec [n_words_total] = the record of each word (n_words_total = the
+// sum of the records' n_words); excluded [P.n_lm] in internal order or nullptr (none). Every word of
+// bits is written.
+void launch_covis_bits(const DevProblem& P, const CovisWin* wins, int n_wins, const int32_t* word_rec, int n_words_total,
+                       const uint8_t* excluded, unsigned long long* bits, hipStream_t s);
+// counts: path 0 over items0 [n0] (record indices, lds_bytes = the largest covisLdsBytes among them),
+// path 1 over items1 [n1][3] (record, row tile, column tile <= row tile). Every element of counts and
+// n_observed of the listed records is written.
+void launch_covis_counts(const CovisWin* wins, const int32_t* items0, int n0, size_t lds_bytes, const int32_t* items1,
+                         int n1, const unsigned long long* bits, int32_t* counts, int32_t* n_observed, hipStream_t s);
+
 }  // namespace okg

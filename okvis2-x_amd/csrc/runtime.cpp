@@ -213,6 +213,10 @@ struct okvisgpu_ctx {
   // owned by the context, outside the arena table, allocated on first use and grown as needed
   void* lmScratch = nullptr;
   size_t lmScratchBytes = 0;
+  // okvisgpu_covisibilities' device arrays (window records | work items | exclusion mask | bitset |
+  // counts | n_observed): likewise the context's own, outside the arena table, grown as needed
+  void* covisScratch = nullptr;
+  size_t covisScratchBytes = 0;
 
   void fillSummaries(const std::vector<WinState>& st, okvisgpu_summary* sums) {
     if (!sums) return;
@@ -271,6 +275,7 @@ struct okvisgpu_ctx {
     if (hostIn) (void)hipHostFree(hostIn);
     if (hostOut) (void)hipHostFree(hostOut);
     if (lmScratch) (void)hipFree(lmScratch);
+    if (covisScratch) (void)hipFree(covisScratch);
     for (hipEvent_t e : forkEv) (void)hipEventDestroy(e);
     for (hipStream_t q : side)
       if (q) (void)hipStreamDestroy(q);
@@ -703,6 +708,131 @@ struct okvisgpu_ctx {
         const size_t ob = (size_t)B.obs_base[w];
         for (int k = 0; k < p->n_observations; ++k) u.obs_error[B.obs_orig[ob + k]] = hErr[ob + k];
       }
+    });
+  }
+
+  // ViGraph::computeCovisibilities on the structure of the last set_problems
+  // (okvisgpu_covisibilities): a record per window that has states, landmarks and observations, the
+  // record of every 64-landmark word (k_covis_bits' work list), the work lists of the two count
+  // kernels (covisFitsLds picks a window's), the caller's exclusion masks
+  // permuted into internal landmark order; all of it packed into pinned memory and uploaded as one
+  // copy. k_covis_bits writes every word of the bitset and the count kernels every element of
+  // counts / n_observed, so nothing is cleared. One copy back per output, then a threaded scatter;
+  // the pair and visibility totals are taken on the host. Reads no parameter value and writes neither
+  // the caller's problem arrays nor the arena.
+  void covisibilities(okvisgpu_covisibility* V) {
+    const int nwin = B.n_win;
+    std::vector<CovisWin> recs;
+    std::vector<int> recOf((size_t)nwin, -1);
+    std::vector<int32_t> items0, items1, wordRec;  // wordRec: the record of each 64-landmark word
+    size_t lds0 = 0;
+    int64_t words = 0, bitsTot = 0, cntTot = 0, stateTot = 0;
+    bool anyMask = false;
+    for (int w = 0; w < nwin; ++w) {
+      const okvisgpu_problem* p = probs[w];
+      V[w].n_pairs = V[w].n_visible = V[w].any = V[w].path = 0;
+      if (p->n_poses <= 0 || p->n_landmarks <= 0 || p->n_observations <= 0) {  // all zeros, nothing to launch
+        const size_t S = (size_t)std::max(p->n_poses, 0);
+        if (V[w].counts) std::memset(V[w].counts, 0, 4 * S * S);
+        if (V[w].n_observed) std::memset(V[w].n_observed, 0, 4 * S);
+        if (V[w].visible) std::memset(V[w].visible, 0, S);
+        continue;
+      }
+      CovisWin r{};
+      r.lm_begin = B.lm_base[w];
+      r.n_lm = p->n_landmarks;
+      r.pose_begin = B.pose_base[w];
+      r.n_state = p->n_poses;
+      r.word_begin = (int32_t)words;
+      r.n_words = (p->n_landmarks + 63) / 64;
+      r.state_off = (int32_t)stateTot;
+      r.bits_off = bitsTot;
+      r.counts_off = cntTot;
+      const int idx = (int)recs.size();
+      if (covisFitsLds(r.n_state, r.n_words)) {
+        items0.push_back(idx);
+        lds0 = std::max(lds0, covisLdsBytes(r.n_state, r.n_words));
+      } else {
+        V[w].path = 1;
+        const int T = (r.n_state + kCovisTile - 1) / kCovisTile;
+        for (int ti = 0; ti < T; ++ti)
+          for (int tj = 0; tj <= ti; ++tj) items1.insert(items1.end(), {idx, ti, tj});
+      }
+      wordRec.insert(wordRec.end(), (size_t)r.n_words, idx);
+      words += r.n_words;
+      stateTot += r.n_state;
+      bitsTot += (int64_t)r.n_state * r.n_words;
+      cntTot += (int64_t)r.n_state * r.n_state;
+      anyMask = anyMask || V[w].landmark_excluded != nullptr;
+      recOf[w] = idx;
+      recs.push_back(r);
+    }
+    if (recs.empty()) return;
+
+    // device: uploaded part (records | word records | items0 | items1 | mask), then bits | counts | n_observed
+    const size_t nl = (size_t)P.n_lm;
+    Arena A;
+    const size_t oRec = A.reserve(sizeof(CovisWin) * recs.size()), oWr = A.reserve(4 * wordRec.size()),
+                 oI0 = A.reserve(4 * items0.size()), oI1 = A.reserve(4 * items1.size()), oEx = A.reserve(anyMask ? nl : 0);
+    const size_t upBytes = A.size;
+    const size_t oBits = A.reserve(8 * (size_t)bitsTot), oCnt = A.reserve(4 * (size_t)cntTot),
+                 oObs = A.reserve(4 * (size_t)stateTot);
+    if (A.size > covisScratchBytes) {
+      if (covisScratch) HIPCHK(hipFree(covisScratch));
+      covisScratch = nullptr;
+      covisScratchBytes = 0;
+      HIPCHK(hipMalloc(&covisScratch, A.size));
+      covisScratchBytes = A.size;
+    }
+    char* dev = static_cast<char*>(covisScratch);
+    // pinned: the uploaded part as on the device, then counts | n_observed as they come back
+    const size_t hCntOff = (upBytes + 255) & ~size_t(255), hObsOff = hCntOff + 4 * (size_t)cntTot;
+    char* host = paramStage(hObsOff + 4 * (size_t)stateTot);
+    std::memcpy(host + oRec, recs.data(), sizeof(CovisWin) * recs.size());
+    std::memcpy(host + oWr, wordRec.data(), 4 * wordRec.size());
+    if (!items0.empty()) std::memcpy(host + oI0, items0.data(), 4 * items0.size());
+    if (!items1.empty()) std::memcpy(host + oI1, items1.data(), 4 * items1.size());
+    if (anyMask)
+      forWindows(nwin, [&](int w) {
+        const okvisgpu_problem* p = probs[w];
+        uint8_t* ex = reinterpret_cast<uint8_t*>(host + oEx) + (size_t)B.lm_base[w];
+        const uint8_t* in = V[w].landmark_excluded;
+        const int* perm = &B.lm_perm[B.lm_base[w]];
+        if (!in) std::memset(ex, 0, (size_t)std::max(p->n_landmarks, 0));
+        else
+          for (int k = 0; k < p->n_landmarks; ++k) ex[k] = in[perm[k]] ? 1 : 0;
+      });
+    HIPCHK(hipMemcpyAsync(dev, host, upBytes, hipMemcpyHostToDevice, stream));
+    const CovisWin* dRec = reinterpret_cast<const CovisWin*>(dev + oRec);
+    unsigned long long* dBits = reinterpret_cast<unsigned long long*>(dev + oBits);
+    int32_t *dCnt = reinterpret_cast<int32_t*>(dev + oCnt), *dObs = reinterpret_cast<int32_t*>(dev + oObs);
+    launch_covis_bits(P, dRec, (int)recs.size(), reinterpret_cast<const int32_t*>(dev + oWr), (int)words,
+                      anyMask ? reinterpret_cast<const uint8_t*>(dev + oEx) : nullptr, dBits, stream);
+    launch_covis_counts(dRec, reinterpret_cast<const int32_t*>(dev + oI0), (int)items0.size(), lds0,
+                        reinterpret_cast<const int32_t*>(dev + oI1), (int)(items1.size() / 3), dBits, dCnt, dObs, stream);
+    HIPCHK(hipGetLastError());
+    const int32_t* hCnt = reinterpret_cast<const int32_t*>(host + hCntOff);
+    const int32_t* hObs = reinterpret_cast<const int32_t*>(host + hObsOff);
+    HIPCHK(hipMemcpyAsync(host + hCntOff, dCnt, 4 * (size_t)cntTot, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(host + hObsOff, dObs, 4 * (size_t)stateTot, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    forWindows(nwin, [&](int w) {
+      if (recOf[w] < 0) return;
+      const CovisWin& r = recs[(size_t)recOf[w]];
+      okvisgpu_covisibility& v = V[w];
+      const size_t S = (size_t)r.n_state;
+      const int32_t *c = hCnt + r.counts_off, *o = hObs + r.state_off;
+      if (v.counts) std::memcpy(v.counts, c, 4 * S * S);
+      if (v.n_observed) std::memcpy(v.n_observed, o, 4 * S);
+      int pairs = 0, vis = 0;
+      for (size_t i = 0; i < S; ++i) {
+        vis += o[i] > 0;
+        if (v.visible) v.visible[i] = o[i] > 0 ? 1 : 0;
+        for (size_t j = i + 1; j < S; ++j) pairs += c[i * S + j] > 0;
+      }
+      v.n_pairs = pairs;
+      v.n_visible = vis;
+      v.any = pairs > 0 ? 1 : 0;
     });
   }
 
@@ -1646,6 +1776,17 @@ int okvisgpu_update_landmarks(okvisgpu_ctx* c, okvisgpu_landmark_update* updates
   return guarded(c, [&]() {
     HIPCHK(hipSetDevice(c->device));
     c->updateLandmarks(updates);
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_covisibilities(okvisgpu_ctx* c, okvisgpu_covisibility* out) {
+  if (!c || !out) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "covisibilities: bad arguments");
+  if (!c->haveProblem) return fail(c, OKVISGPU_ERR_NO_PROBLEM, "no problem set");
+  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "covisibilities: call after solve_end");
+  return guarded(c, [&]() {
+    HIPCHK(hipSetDevice(c->device));
+    c->covisibilities(out);
     return (int)OKVISGPU_OK;
   });
 }

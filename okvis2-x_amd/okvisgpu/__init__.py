@@ -202,6 +202,12 @@ class LandmarkUpdate(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class Covisibility(C.Structure):
+    """okvisgpu_covisibility: one window's exclusion mask and outputs of okvisgpu_covisibilities."""
+    _fields_ = [("landmark_excluded", _up), ("counts", _ip), ("n_observed", _ip), ("visible", _up),
+                ("n_pairs", C.c_int32), ("n_visible", C.c_int32), ("any", C.c_int32), ("path", C.c_int32)]
+
+
 # Exported symbols of include/okvisgpu.h (checked by tests/test_abi.py).
 EXPORTED_SYMBOLS = [
     "okvisgpu_abi_version", "okvisgpu_default_options", "okvisgpu_device_count", "okvisgpu_ctx_create",
@@ -216,7 +222,7 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_graph_load", "okvisgpu_graph_problem", "okvisgpu_graph_ids", "okvisgpu_graph_destroy",
     "okvisgpu_graph_save", "okvisgpu_get_stats", "okvisgpu_synth_true_extrinsics", "okvisgpu_imu_append",
     "okvisgpu_eval_host", "okvisgpu_plan_window", "okvisgpu_loss_evaluate", "okvisgpu_plan_digest",
-    "okvisgpu_launch_regime", "okvisgpu_update_landmarks",
+    "okvisgpu_launch_regime", "okvisgpu_update_landmarks", "okvisgpu_covisibilities",
 ]
 N_PHASES = 15
 
@@ -283,6 +289,7 @@ def lib():
         L.okvisgpu_twopose_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _dp, _dp]
         L.okvisgpu_loss_evaluate.argtypes = [C.POINTER(Loss), C.c_double, _dp]
         L.okvisgpu_update_landmarks.argtypes = [C.c_void_p, C.POINTER(LandmarkUpdate)]
+        L.okvisgpu_covisibilities.argtypes = [C.c_void_p, C.POINTER(Covisibility)]
         _lib = L
     return _lib
 
@@ -753,6 +760,40 @@ class Context:
         for u, d in zip(ups, out):
             d["initialised"], d["reset"] = d["initialised"].astype(bool), d["reset"].astype(bool)
             d["n_initialised"], d["n_reset"], d["in_front"] = int(u.n_initialised), int(u.n_reset), bool(u.in_front)
+        return out
+
+    def covisibilities(self, excluded=None, n_windows: Optional[int] = None):
+        """okvisgpu_covisibilities (ViGraph::computeCovisibilities on the structure of the last
+        set_problems): one dict per window with counts [S, S] (int32, symmetric, zero diagonal),
+        n_observed [S], visible [S] (bool), n_pairs, n_visible, any (bool) and path (0 window in LDS,
+        1 tiled), in the caller's pose indices. `excluded`: None, or per window None or a
+        [n_landmarks] mask of the landmarks to leave out (a single array for a single window)."""
+        n = self._n_windows(n_windows)
+        if excluded is None:
+            excluded = [None] * n
+        elif n == 1 and not isinstance(excluded, (list, tuple)):
+            excluded = [excluded]
+        if len(excluded) != n:
+            raise ValueError(f"{len(excluded)} exclusion masks for {n} windows")
+        vs = (Covisibility * n)()
+        out, keep = [], []
+        for v, p, ex in zip(vs, self._keep[1], excluded):
+            S = p.n_poses
+            d = {"counts": np.zeros((S, S), dtype=np.int32), "n_observed": np.zeros(S, dtype=np.int32),
+                 "visible": np.zeros(S, dtype=np.uint8)}
+            if ex is not None:
+                ex = np.ascontiguousarray(np.asarray(ex) != 0, dtype=np.uint8)
+                if ex.shape != (p.n_landmarks,):
+                    raise ValueError(f"exclusion mask of shape {ex.shape} for {p.n_landmarks} landmarks")
+                keep.append(ex)
+                v.landmark_excluded = ex.ctypes.data_as(_up)
+            v.counts, v.n_observed = d["counts"].ctypes.data_as(_ip), d["n_observed"].ctypes.data_as(_ip)
+            v.visible = d["visible"].ctypes.data_as(_up)
+            out.append(d)
+        self._check(lib().okvisgpu_covisibilities(self.h, vs), "okvisgpu_covisibilities")
+        for v, d in zip(vs, out):
+            d["visible"] = d["visible"].astype(bool)
+            d["n_pairs"], d["n_visible"], d["any"], d["path"] = int(v.n_pairs), int(v.n_visible), bool(v.any), int(v.path)
         return out
 
     def close(self):
