@@ -69,9 +69,11 @@ __device__ __forceinline__ bool linSelect(const DevProblem& P, int w, int lin_mo
 //   visit    J_p, J_l of its 1-2 residuals from the stored linearisation (r | A) -> W = J_p^T J_l,
 //            H = J_p^T J_p and g = J_p^T r (stored for k_fgrad / k_assemble_pp), and its share
 //            of V = J_l^T J_l, g_l = J_l^T r (LDS)
-//   landmark (one thread each) V, g_l summed over its visits in visit order; iteration 0: the
-//            Jacobi scaling 1 / (1 + sqrt(diag V)); then the 3x3 LLT of s V s + mu D^2
+//   landmark (one thread each, wavefront 0) V, g_l summed over its visits in visit order; iteration
+//            0: the Jacobi scaling 1 / (1 + sqrt(diag V)); then the 3x3 LLT of s V s + mu D^2
 //            (InvertPSDMatrix) -> L^-1, zz = L^-1 (s g), the dogleg diagonal D
+//   segments (beside the landmark phase, wavefronts 1..3) H[0..8] of each (group, free pose) summed
+//            over its visits; then (all wavefronts) H[9..20] | g_p
 //   visit    Z = s_p W s_l L^-T and U z = Z zz, the operands of the Schur terms
 //            Y_a U_b^T = Z_a Z_b^T (the partial blocks below; Z never leaves the workgroup)
 // The barriers order LDS only (ldsBarrier): no thread reads global data another thread of the
@@ -105,11 +107,20 @@ static_assert(kPartRows == 2 || kPartRows == 3, "OKG_PART_ROWS must be 2 or 3");
 // the products with the pose visits' Z exactly like a pose visit; V / g_l come from the pose visits.
 // (the body of one landmark group grp; the kernels below run it per workgroup or per window loop)
 // LDS of lmVisitGroup at namespace scope: one allocation per kernel whatever modes it runs
-// (k_lin_few<.., true> runs modes 1 and 2). gLmvBuf rows 0..8: visit shares of V (6) | g_l (3);
-// rows 9..17: visit values being summed into segments; finally rows 0..17: the visits' Z for the
-// partial Schur blocks. gLmvLz per landmark: L^-1 (9) | zz (3) | s_l (3). gLmvPC: the group's
-// landmark-pair products (a | b << 16).
-__shared__ double gLmvBuf[18][kLmGroupVisits];
+// (k_lin_few<.., true> runs modes 1 and 2). gLmvBuf rows 0..8: visit shares of V (6) | g_l (3),
+// beside them rows 9..17: H[0..8] by slot (the first segment chunk); then rows 0..17: H[9..20] | g_p
+// by slot (the second chunk); rows 9..14: U z by slot; finally the whole buffer as a flat
+// [kLmGroupVisits][kVisitZ] array: the visits' Z for the partial Schur blocks. gLmvLz per
+// landmark: L^-1 (9) | zz (3) | s_l (3). gLmvPC: the group's landmark-pair products (a | b << 16).
+// Row stride of gLmvBuf: kLmGroupVisits + 1 doubles. A stride of kLmGroupVisits (2,048 B) is a
+// multiple of the 256 B the 64 LDS banks span, so column m of all 18 rows would share one bank pair,
+// and the lanes of a segment sum (one row each, same columns in lock-step) would serialise 18-fold.
+// With 257 doubles row i starts 2 i banks further on: 18 distinct bank pairs. The flat visit-major
+// view of the last phase ([kLmGroupVisits][kVisitZ]) still fits below the 18 rows.
+constexpr int kLmvStride = kLmGroupVisits + 1;
+static_assert(18 * kLmvStride >= kVisitZ * kLmGroupVisits, "the flat Z view fits in gLmvBuf");
+static_assert((kLmvStride * 8) % 256 == 8, "consecutive rows are one bank pair apart");
+__shared__ double gLmvBuf[18][kLmvStride];
 __shared__ double gLmvLz[15][kLmGroupMax];
 __shared__ int gLmvPC[kLmPartStage];
 template <int mode, bool EXT>
@@ -118,11 +129,11 @@ __device__ __forceinline__ void lmVisitGroup(const DevProblem& P, const int grp)
   const auto gi = gmem(reinterpret_cast<const int4*>(P.lmg_info + kLmgInfo * grp));
   const int4 gi0 = gi[0], gi1 = gi[kLmgInfo / 4];
   const int l0 = gi0.x, l1 = gi1.x, v0 = gi0.y, v1 = gi1.y;
-  double (*sBuf)[kLmGroupVisits] = gLmvBuf;
+  double (*sBuf)[kLmvStride] = gLmvBuf;
   double (*sLz)[kLmGroupMax] = gLmvLz;
   int* sPC = gLmvPC;
-  double (*sVg)[kLmGroupVisits] = sBuf;
-  double (*sR)[kLmGroupVisits] = sBuf + 9;
+  double (*sVg)[kLmvStride] = sBuf;
+  double (*sR)[kLmvStride] = sBuf + 9;
   const int w = gi0.z;                       // a group never spans windows
   const int v = v0 + t;
   const bool hasV = v < v1;
@@ -167,6 +178,10 @@ __device__ __forceinline__ void lmVisitGroup(const DevProblem& P, const int grp)
   // segment bookkeeping (consumed after the landmark phase)
   const int sg0 = gi0.w, nseg = gi1.w - sg0;
   const int slot = hasV ? vSlot : (hasX ? P.xvisit_slot[xv] : -1);
+  // (wavefronts 1..3 sum the first segment chunk, 9 values per segment, beside the landmark phase)
+  const auto gsr = gmem(reinterpret_cast<const int2*>(P.seg_range));
+  const int sgl = max(nseg - 1, 0);
+  constexpr int kSegAThreads = kLmGroupVisits - 64;
   double W[18], H[21], gp[6], Vv[6], gl[3];
 #pragma unroll
   for (int i = 0; i < 18; ++i) W[i] = 0.0;
@@ -274,18 +289,26 @@ __device__ __forceinline__ void lmVisitGroup(const DevProblem& P, const int grp)
       }
     }
   }
+  // The visit's shares of V | g_l go to rows 0..8 in visit order (the landmark phase sums them);
+  // H[0..8] go to the visit's slot in rows 9..17, where every segment is a contiguous range: the
+  // first segment chunk, summed beside the landmark phase. (The GN prep reuses V, g_l and the
+  // segments' H | g of the linearisation.)
+  const int2 rA = gsr[sg0 + min(max(t - 64, 0) / 9, sgl)];  // first range of the first chunk, in flight over the LDS stores
+  if (mode != 2) {
 #pragma unroll
-  for (int i = 0; i < 6; ++i) sVg[i][t] = Vv[i];
+    for (int i = 0; i < 6; ++i) sVg[i][t] = Vv[i];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) sVg[6 + i][t] = gl[i];
+    for (int i = 0; i < 3; ++i) sVg[6 + i][t] = gl[i];
+    if (slot >= 0)
+#pragma unroll
+      for (int i = 0; i < 9; ++i) sR[i][slot] = H[i];
+  }
   ldsBarrier();
   LCLK(0)
   // Operands of the later phases, issued now so that they land during the landmark phase: this
-  // thread's first segment ranges in the three segment passes (18, 9 and 6 values per segment) and
+  // thread's first segment ranges in the other two segment passes (18 and 6 values per segment) and
   // the pose scaling of its visit (a valid dummy address when the pose is not free).
-  const auto gsr = gmem(reinterpret_cast<const int2*>(P.seg_range));
-  const int sgl = max(nseg - 1, 0);
-  const int2 rA = gsr[sg0 + min(t / 18, sgl)], rB = gsr[sg0 + min(t / 9, sgl)], rC = gsr[sg0 + min(t / 6, sgl)];
+  const int2 rB = gsr[sg0 + min(t / 18, sgl)], rC = gsr[sg0 + min(t / 6, sgl)];
   // (and this thread's first partial block's product range)
   const int pfi = npart > 0 ? pg0 + min(t / kPartThreads, npart - 1) : 0;  // (index 1 exists: >= 8-byte arrays)
   const int pcA = gmem(P.part_cbegin)[pfi], pcB = gmem(P.part_cbegin)[pfi + 1];
@@ -398,37 +421,41 @@ __device__ __forceinline__ void lmVisitGroup(const DevProblem& P, const int grp)
         }
       }
     }
+  } else if (mode != 2 && t >= 64) {
+    // ---- beside the landmark phase (wavefront 0), wavefronts 1..3: the first segment chunk, H[0..8]
+    // of each (group, free pose) summed over its visits (visits were scattered to their slots, so
+    // every segment is a contiguous LDS range)
+    const int q = t - 64;
+    if (q < nseg * 9) {  // first pass: the prefetched range
+      const int sgi = q / 9, i = q - sgi * 9;
+      gmemw(P.seg_hg)[(size_t)(sg0 + sgi) * kSegHG + i] = rangeSum(sR[i], rA.x, rA.y);
+    }
+    for (int e = q + kSegAThreads; e < nseg * 9; e += kSegAThreads) {
+      const int sgi = e / 9, i = e - sgi * 9;
+      const int m0 = gmem(P.seg_range)[2 * (sg0 + sgi)], m1 = gmem(P.seg_range)[2 * (sg0 + sgi) + 1];
+      gmemw(P.seg_hg)[(size_t)(sg0 + sgi) * kSegHG + i] = rangeSum(sR[i], m0, m1);
+    }
   }
   ldsBarrier();
   LCLK(1)
-  asm volatile("" ::"v"(rA.x), "v"(rA.y), "v"(rB.x), "v"(rB.y), "v"(rC.x), "v"(rC.y), "v"(pcA),
-               "v"(pcB));  // (not sunk into branches)
-  // ---- segments: H | g of each (group, free pose) summed over its visits (visits are scattered
-  // to their slots so that every segment is a contiguous LDS range). The visit shares of V / g_l
-  // are consumed, so all 18 rows of sBuf take values: H[0..17], then H[18..20] | g_p.
+  asm volatile("" ::"v"(rB.x), "v"(rB.y), "v"(rC.x), "v"(rC.y), "v"(pcA), "v"(pcB));  // (not sunk into branches)
+  // ---- the second segment chunk: the visit shares of V / g_l and the first chunk are consumed, so
+  // all 18 rows of sBuf take the remaining values, H[9..20] | g_p, in one pass
   if (mode != 2) {
+    if (slot >= 0)
 #pragma unroll
-    for (int chunk = 0; chunk < 2; ++chunk) {
-      const int nval = chunk == 0 ? 18 : 9;
-      if (slot >= 0)
-#pragma unroll
-        for (int i = 0; i < nval; ++i) {
-          const int e = 18 * chunk + i;
-          sBuf[i][slot] = e < 21 ? H[e] : gp[e - 21];
-        }
-      ldsBarrier();
-      if (t < nseg * nval) {  // first pass: the prefetched range
-        const int sgi = t / nval, i = t - sgi * nval;
-        const int2 r = chunk == 0 ? rA : rB;
-        gmemw(P.seg_hg)[(size_t)(sg0 + sgi) * kSegHG + 18 * chunk + i] = rangeSum(sBuf[i], r.x, r.y);
-      }
-      for (int e = t + kLmGroupVisits; e < nseg * nval; e += kLmGroupVisits) {
-        const int sgi = e / nval, i = e - sgi * nval;
-        const int m0 = gmem(P.seg_range)[2 * (sg0 + sgi)], m1 = gmem(P.seg_range)[2 * (sg0 + sgi) + 1];
-        gmemw(P.seg_hg)[(size_t)(sg0 + sgi) * kSegHG + 18 * chunk + i] = rangeSum(sBuf[i], m0, m1);
-      }
-      ldsBarrier();
+      for (int i = 0; i < 18; ++i) sBuf[i][slot] = i < 12 ? H[9 + i] : gp[i - 12];
+    ldsBarrier();
+    if (t < nseg * 18) {  // first pass: the prefetched range
+      const int sgi = t / 18, i = t - sgi * 18;
+      gmemw(P.seg_hg)[(size_t)(sg0 + sgi) * kSegHG + 9 + i] = rangeSum(sBuf[i], rB.x, rB.y);
     }
+    for (int e = t + kLmGroupVisits; e < nseg * 18; e += kLmGroupVisits) {
+      const int sgi = e / 18, i = e - sgi * 18;
+      const int m0 = gmem(P.seg_range)[2 * (sg0 + sgi)], m1 = gmem(P.seg_range)[2 * (sg0 + sgi) + 1];
+      gmemw(P.seg_hg)[(size_t)(sg0 + sgi) * kSegHG + 9 + i] = rangeSum(sBuf[i], m0, m1);
+    }
+    ldsBarrier();
   }
   LCLK(2)
   if (mode == 0) return;
