@@ -441,6 +441,42 @@ typedef struct okvisgpu_imu_append_batch {
 } okvisgpu_imu_append_batch;
 int okvisgpu_imu_append(okvisgpu_ctx* ctx, const okvisgpu_imu_append_batch* batch, int32_t* steps);
 
+/* ---------------------------------------------------------------- IMU propagation
+ * (An addition to ABI 6: a new entry point and a new struct; OKVISGPU_ABI_VERSION stays 6.)
+ * The static ImuError::propagation (ImuError.cpp:537-759) for a batch of independent items on the
+ * GPU: what ViGraph::addStatesPropagate (ViGraph.cpp:400-417) and ThreadedSlam::processFrame
+ * (ThreadedSlam.cpp:613-627) call for the new state's pose and speed, and Frontend::propagation
+ * (Frontend.cpp:1146-1162) with the 15x15 covariance and Jacobian. Per item i: poses[i] (T_WS as
+ * [r, q xyzw]) and speed_biases[i] at t_start are replaced by the propagated pose and speed at t_end
+ * (the biases are unchanged), integrating the item's samples with the trapezoid chain of :644-668
+ * and the stepping rules of :584-617 and :716-721 (interpolation at both ends, steps with dt <= 0
+ * skipped, dt from integer nanosecond differences). covariance / jacobian (each may be NULL) receive
+ * P = T P_delta T^T (:748-757; per-step noise with the saturation factors of :619-640 and :688-707)
+ * and F (:735-746) in the error-state order [r, alpha, v, b_g, b_a], row-major. steps[i] (steps may
+ * be NULL) is the number of integrated steps, or -1 when the item's last sample is older than t_end
+ * (:552-553): then nothing of the item is written, covariance and Jacobian rows included. With 0
+ * steps (t_end <= t_start) the pose and speed/bias keep their bits, the Jacobian is the identity
+ * and the covariance zero. An item without samples, or whose first sample is newer than t_start
+ * (the reference's assertion at :550), makes the whole call return OKVISGPU_ERR_INVALID_ARGUMENT
+ * before anything is launched or written; okvisgpu_last_error names the item. Also refused between
+ * okvisgpu_solve_begin and _solve_end. Uses the context's device and stream and returns with the
+ * results in the caller's arrays; independent of the problem set with okvisgpu_set_problems (needs
+ * none, leaves the device parameter sets alone). An item's result does not depend on the batch. */
+typedef struct okvisgpu_imu_propagate_batch {
+  int32_t n;
+  okvisgpu_imu_params imu_params;
+  double* poses;                    /* [n][7] T_WS, in/out                                         */
+  double* speed_biases;             /* [n][9] in/out (only v changes)                              */
+  const int64_t* t_start_ns;        /* [n]                                                         */
+  const int64_t* t_end_ns;          /* [n]                                                         */
+  const int32_t* sample_begin;      /* [n+1] CSR into the sample arrays                            */
+  const int64_t* sample_t_ns;       /* [n_samples]                                                 */
+  const double*  sample_gyr_acc;    /* [n_samples][6]                                              */
+  double* covariance;               /* [n][225] row-major, out, may be NULL                        */
+  double* jacobian;                 /* [n][225] row-major, out, may be NULL                        */
+} okvisgpu_imu_propagate_batch;
+int okvisgpu_imu_propagate(okvisgpu_ctx* ctx, const okvisgpu_imu_propagate_batch* batch, int32_t* steps);
+
 /* ---------------------------------------------------------------- post-solve landmark pass
  * (An addition to ABI 6: a new entry point and a new struct; no existing struct or call changes, so
  * OKVISGPU_ABI_VERSION stays 6 and a caller built against the earlier header keeps working.)

@@ -1,0 +1,443 @@
+// kernels_imu_propagate.hip — ImuError::propagation (ImuError.cpp:537-759) for a batch of
+// independent items on gfx950 (FP64): pose and speed of the next state from the previous estimate and
+// the IMU samples between two stamps, with the optional 15x15 Jacobian and covariance.
+//
+//  k_imu_propagate_lane     one lane per item (64 per wavefront): the call without covariance and
+//                           Jacobian (ViGraph::addStatesPropagate, ThreadedSlam::processFrame). Only
+//                           Delta_q, acc_integral and acc_doubleintegral are carried; nothing of the
+//                           bias Jacobians or the covariance is computed.
+//  k_imu_propagate_group<COV>  one 16-lane group per item (four per wavefront), the layout of
+//                           k_eval_imu: every lane of the group runs the scalar chain (:644-668), so
+//                           the block-sparse F_delta (:672-682) is register resident; lane l < 15 owns
+//                           column l of P_delta and P <- F P F^T + Q takes one LDS transpose per step.
+//                           COV = false does no covariance work (Jacobian only).
+//
+// An item's arithmetic does not depend on the batch or on its position in it: loops run to the
+// wavefront's longest item with the shorter ones predicated off, and no lane reads another item's
+// data. An item whose samples do not reach t_end gets steps = -1 and nothing else is written
+// (:552-553); an item with no integrated step keeps its pose and speed/bias bits (Jacobian = I,
+// covariance = 0).
+#include "imu_fdelta.hpp"
+#include "launch.hpp"
+#include "okvisgpu_math.hpp"
+
+namespace okg {
+
+namespace {
+
+struct PropItem {  // one item's record, loaded once
+  int64_t t_start, t_end;
+  int sbeg, N;
+  bool covered;
+};
+
+__device__ __forceinline__ PropItem loadItem(const ImuPropagateDev& A, int i) {
+  PropItem it;
+  it.t_start = gmem(A.t_start)[i];
+  it.t_end = gmem(A.t_end)[i];
+  it.sbeg = gmem(A.sbegin)[i];
+  it.N = gmem(A.sbegin)[i + 1] - it.sbeg;
+  // imuMeasurements.back().timeStamp >= end (:552); the host has refused N == 0
+  it.covered = it.N > 0 && gmem(A.ts)[it.sbeg + max(it.N - 1, 0)] >= it.t_end;
+  return it;
+}
+
+// One pass of the sample loop up to the integrity check (:584-640) for sample k of an item whose
+// integration time is `time`: false when the sample is skipped (dt <= 0, :607-609). On true: dt, the
+// (interpolated) measurements, the step's end `nexttime` and the saturation flags.
+struct PropStep {
+  double dt, w[3], a[3];  // dt, omega_S_true, acc_S_true (:645, :655)
+  bool gyr_sat, acc_sat;
+  int64_t nexttime;
+};
+struct RawSample {  // one sample as stored: stamp, gyro, accelerometer
+  int64_t t;
+  double ga[6];
+};
+// Sample min(k, N - 1) of the item. The loops keep samples k and k + 1 in registers and load sample
+// k + 2 at the top of step k, so that a step does not begin by waiting for its own loads. (Past the
+// end the last sample stands in: the reference reads nothing it uses there, such a step has dt <= 0.)
+__device__ __forceinline__ RawSample loadSample(const ImuPropagateDev& A, const PropItem& it, int k) {
+  const int s = it.sbeg + min(k, it.N - 1);
+  RawSample r;
+  r.t = gmem(A.ts)[s];
+  const auto g = gmem(A.ga + 6 * (size_t)s);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) r.ga[j] = g[j];
+  return r;
+}
+__device__ __forceinline__ bool propSample(const ImuPropagateDev& A, const PropItem& it, int k, const RawSample& cur,
+                                           const RawSample& nxt, int64_t time, bool started, const double* bg,
+                                           const double* ba, PropStep& s) {
+  const bool last = k + 1 == it.N;
+  double om0[3], ac0[3], om1[3], ac1[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    om0[j] = cur.ga[j];
+    ac0[j] = cur.ga[3 + j];
+    om1[j] = nxt.ga[j];
+    ac1[j] = nxt.ga[3 + j];
+  }
+  const int64_t ts0 = cur.t;
+  int64_t nexttime = last ? it.t_end : nxt.t;
+  double dt = durToSec(nexttime - time);
+  if (it.t_end < nexttime) {  // clip to t_end, interpolate the second measurement (:598-605)
+    const double interval = durToSec(nexttime - ts0);
+    nexttime = it.t_end;
+    dt = durToSec(nexttime - time);
+    const double r = dt / interval;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      om1[j] = (1.0 - r) * om0[j] + r * om1[j];
+      ac1[j] = (1.0 - r) * ac0[j] + r * ac1[j];
+    }
+  }
+  if (!(dt > 0.0)) return false;
+  if (!started) {  // the first integrated step starts at t_start (:612-617)
+    const double r = dt / durToSec(nexttime - ts0);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      om0[j] = r * om0[j] + (1.0 - r) * om1[j];
+      ac0[j] = r * ac0[j] + (1.0 - r) * ac1[j];
+    }
+  }
+  const double g_max = A.par[1], a_max = A.par[0];
+  s.gyr_sat = false;
+  s.acc_sat = false;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    s.gyr_sat = s.gyr_sat || fabs(om0[j]) > g_max || fabs(om1[j]) > g_max;
+    s.acc_sat = s.acc_sat || fabs(ac0[j]) > a_max || fabs(ac1[j]) > a_max;
+    s.w[j] = 0.5 * (om0[j] + om1[j]) - bg[j];
+    s.a[j] = 0.5 * (ac0[j] + ac1[j]) - ba[j];
+  }
+  s.dt = dt;
+  s.nexttime = nexttime;
+  return true;
+}
+
+// dq of one step (:644-650) and sin / cos of theta_half for the right Jacobian
+__device__ __forceinline__ Q stepDq(const PropStep& s, double& sh, double& ch) {
+  const double theta_half = sqrt(s.w[0] * s.w[0] + s.w[1] * s.w[1] + s.w[2] * s.w[2]) * 0.5 * s.dt;
+  sincos(theta_half, &sh, &ch);
+  double sincv;  // ode::sinc (ode.hpp:34-46)
+  if (fabs(theta_half) > 1.0e-6) {
+    sincv = sh / theta_half;
+  } else {
+    const double x_2 = theta_half * theta_half, x_4 = x_2 * x_2, x_6 = x_2 * x_2 * x_2;
+    sincv = 1.0 - (1.0 / 6.0) * x_2 + (1.0 / 120.0) * x_4 - (1.0 / 5040.0) * x_6;
+  }
+  const double sth = sincv * 0.5 * s.dt;
+  return Q{sth * s.w[0], sth * s.w[1], sth * s.w[2], ch};
+}
+
+// The outputs that need no Jacobian (:726-732), written by one lane: r_1, q_1 = normalize(q_0 Dq)
+// (Transformation::set normalises) and v_1.
+__device__ __forceinline__ void writeState(const ImuPropagateDev& A, int i, const Q& q0, const double* C0,
+                                           const double* v0, const Q& Dq, const double* ai, const double* adi,
+                                           double Dt) {
+  const auto pose = gmemw(A.poses + 7 * (size_t)i);
+  const auto sb = gmemw(A.sb + 9 * (size_t)i);
+  const double gW[3] = {0.0, 0.0, A.par[6]};
+  double Cadi[3], Cai[3];
+  mv3(C0, adi, Cadi);
+  mv3(C0, ai, Cai);
+  double r1[3], v1[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    r1[j] = pose[j] + v0[j] * Dt + Cadi[j] - 0.5 * gW[j] * Dt * Dt;
+    v1[j] = v0[j] + (Cai[j] - gW[j] * Dt);
+  }
+  const Q q1 = qnormalize(qmul(q0, Dq));
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    pose[j] = r1[j];
+    sb[j] = v1[j];
+  }
+  pose[3] = q1.x; pose[4] = q1.y; pose[5] = q1.z; pose[6] = q1.w;
+}
+
+}  // namespace
+
+// ---- one lane per item: pose and speed only
+__global__ __launch_bounds__(64) void k_imu_propagate_lane(const ImuPropagateDev A) {
+  const int i = (int)(blockIdx.x * 64 + threadIdx.x);
+  if (i >= A.n) return;
+  const PropItem it = loadItem(A, i);
+  if (!it.covered) {
+    gmemw(A.steps)[i] = -1;
+    return;
+  }
+  const auto sbp = gmem(A.sb + 9 * (size_t)i);
+  const double v0[3] = {sbp[0], sbp[1], sbp[2]}, bg[3] = {sbp[3], sbp[4], sbp[5]}, ba[3] = {sbp[6], sbp[7], sbp[8]};
+  Q Dq{0.0, 0.0, 0.0, 1.0};
+  double C[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // R(Delta_q), carried (= qrot(Dq) of the previous step)
+  double ai[3] = {0, 0, 0}, adi[3] = {0, 0, 0}, Dt = 0.0;
+  int64_t time = it.t_start;
+  int steps = 0;
+  RawSample cur = loadSample(A, it, 0), nxt = loadSample(A, it, 1);
+  for (int k = 0; k < it.N; ++k) {
+    const RawSample ahead = loadSample(A, it, k + 2);
+    PropStep s;
+    const bool ok = propSample(A, it, k, cur, nxt, time, steps > 0, bg, ba, s);
+    cur = nxt;
+    nxt = ahead;
+    if (!ok) continue;
+    const double dt = s.dt;
+    Dt += dt;
+    double sh, ch;
+    Dq = qmul(Dq, stepDq(s, sh, ch));
+    double C1[9], CCa[3];
+    qrot(Dq, C1);
+#pragma unroll
+    for (int e = 0; e < 9; ++e) C[e] += C1[e];
+    mv3(C, s.a, CCa);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      adi[j] += ai[j] * dt + 0.25 * CCa[j] * dt * dt;
+      ai[j] += 0.5 * CCa[j] * dt;
+    }
+#pragma unroll
+    for (int e = 0; e < 9; ++e) C[e] = C1[e];
+    time = s.nexttime;
+    ++steps;
+    if (s.nexttime == it.t_end) break;
+  }
+  gmemw(A.steps)[i] = steps;
+  if (steps == 0) return;
+  const auto pose = gmem(A.poses + 7 * (size_t)i);
+  const Q q0 = qnormalize(Q{pose[3], pose[4], pose[5], pose[6]});
+  double C0[9];
+  qrot(q0, C0);
+  writeState(A, i, q0, C0, v0, Dq, ai, adi, Dt);
+}
+
+// ---- one 16-lane group per item: Jacobian, and with COV the covariance
+constexpr int kPropGroup = 16;
+constexpr int kPropPerWG = 4;
+constexpr int kPS = 17;  // row stride of the LDS exchange: lanes walking a column hit distinct banks
+
+template <bool COV>
+__global__ __launch_bounds__(64) void k_imu_propagate_group(const ImuPropagateDev A) {
+  const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+  const int i = (int)blockIdx.x * kPropPerWG + g;
+  __shared__ double sAll[kPropPerWG][15 * kPS];  // per group: the P exchange, then the Jacobian
+  double* const M = sAll[g];
+
+  const bool inR = i < A.n;
+  const int ic = inR ? i : 0;
+  const PropItem it = loadItem(A, ic);
+  const bool live = inR && it.covered;
+  const auto sbp = gmem(A.sb + 9 * (size_t)ic);
+  const double v0[3] = {sbp[0], sbp[1], sbp[2]}, bg[3] = {sbp[3], sbp[4], sbp[5]}, ba[3] = {sbp[6], sbp[7], sbp[8]};
+
+  // the chain (:556-578), on every lane of the group
+  Q Dq{0.0, 0.0, 0.0, 1.0};
+  double C[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  double Ci[9], Cdi[9], cross[9], dadbg[9], dvdbg[9], dpdbg[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) Ci[e] = Cdi[e] = cross[e] = dadbg[e] = dvdbg[e] = dpdbg[e] = 0.0;
+  double ai[3] = {0, 0, 0}, adi[3] = {0, 0, 0}, Dt = 0.0;
+  double Pc[15];  // column l of P_delta
+#pragma unroll
+  for (int e = 0; e < 15; ++e) Pc[e] = 0.0;
+
+  int64_t time = it.t_start;
+  int steps = 0;
+  bool done = !live;
+  // uniform trip count over the wavefront (the barriers of the P exchange); shorter items idle
+  int Nmax = live ? it.N : 0;
+  Nmax = max(Nmax, __shfl_xor(Nmax, 16, 64));
+  Nmax = max(Nmax, __shfl_xor(Nmax, 32, 64));
+  RawSample cur = loadSample(A, it, 0), nxt = loadSample(A, it, 1);
+  for (int k = 0; k < Nmax; ++k) {
+    const RawSample ahead = loadSample(A, it, k + 2);
+    PropStep s;
+    const bool doStep =
+        !done && k < it.N && propSample(A, it, k, cur, nxt, time, steps > 0, bg, ba, s);  // uniform over the group
+    cur = nxt;
+    nxt = ahead;
+    double F[kFdt + 1];
+    if (doStep) {
+      const double dt = s.dt;
+      Dt += dt;
+      double sh, ch;
+      const Q dq = stepDq(s, sh, ch);
+      Dq = qmul(Dq, dq);
+      double C1[9], CC[9], CCa[3];
+      qrot(Dq, C1);
+#pragma unroll
+      for (int e = 0; e < 9; ++e) CC[e] = C[e] + C1[e];
+      mv3(CC, s.a, CCa);
+      // Jacobian parts (:663-668): cross_1 = R(dq)^T cross + rightJacobian(w dt) dt,
+      // X = C [a]x cross + C_1 [a]x cross_1
+      double X[9];
+      {
+        const double wdt[3] = {s.w[0] * dt, s.w[1] * dt, s.w[2] * dt};
+        double Jr[9], Rdqi[9], ax[9], t0[9], t1[9], cross1[9];
+        rightJacobianHalf(wdt, sh, ch, Jr);
+        qrot(qinv(dq), Rdqi);
+        crossMx(s.a, ax);
+        mm3(C, ax, t0);
+        mm3(t0, cross, X);
+        mm3(Rdqi, cross, cross1);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) cross[e] = cross1[e] + Jr[e] * dt;
+        mm3(C1, ax, t0);
+        mm3(t0, cross, t1);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) X[e] += t1[e];
+      }
+      const double qdt2 = 0.25 * dt * dt;
+      // F_delta (:672-682) from the sums before the step, then the sums (:656-668)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const double v = ai[j] * dt + qdt2 * CCa[j];
+        if (COV) {
+          F[kF03 + j] = v;                     // F03 = -[acc_integral dt + dt^2/4 (C + C_1) a]x, held as its vector
+          F[kF63 + j] = 0.5 * dt * CCa[j];     // F63 = -[dt/2 (C + C_1) a]x
+        }
+        adi[j] += v;
+        ai[j] += 0.5 * CCa[j] * dt;
+      }
+#pragma unroll
+      for (int e = 0; e < 9; ++e) {
+        const double p = dt * dvdbg[e] + qdt2 * X[e];
+        if (COV) {
+          F[kF09 + e] = p;
+          F[kF012 + e] = -Ci[e] * dt + qdt2 * CC[e];
+          F[kF39 + e] = -dt * C1[e];
+          F[kF69 + e] = 0.5 * dt * X[e];
+          F[kF612 + e] = -0.5 * dt * CC[e];
+        }
+        Cdi[e] += Ci[e] * dt + qdt2 * CC[e];
+        Ci[e] += 0.5 * dt * CC[e];
+        dadbg[e] += dt * C1[e];  // (no right Jacobian here, unlike redoPreintegration)
+        dpdbg[e] += p;
+        dvdbg[e] += 0.5 * dt * X[e];
+        C[e] = C1[e];
+      }
+      if (COV) F[kFdt] = dt;
+      time = s.nexttime;
+      ++steps;
+      if (s.nexttime == it.t_end) done = true;
+    }
+    if (COV) {
+      // P <- F P F^T + Q (:684-707): M = F P (column l), exchange, P' = F M^T (column l)
+      if (doStep && l < 15) {
+        double Mc[15];
+        applyF(F, Pc, Mc);
+#pragma unroll
+        for (int e = 0; e < 15; ++e) M[l * kPS + e] = Mc[e];
+      }
+      __syncthreads();
+      if (doStep && l < 15) {
+        double Mr[15];
+#pragma unroll
+        for (int e = 0; e < 15; ++e) Mr[e] = M[e * kPS + l];
+        applyF(F, Mr, Pc);
+        const double dt = s.dt;
+        double sg = A.par[2], sa = A.par[3];
+        if (s.gyr_sat) sg *= 100;
+        if (s.acc_sat) sa *= 100;
+        const double s2a = dt * sg * sg, s2v = dt * sa * A.par[3], s2p = 0.5 * dt * dt * s2v;
+        const double s2bg = dt * A.par[4] * A.par[4], s2ba = dt * A.par[5] * A.par[5];
+        const double q = l < 3 ? s2p : (l < 6 ? s2a : (l < 9 ? s2v : (l < 12 ? s2bg : s2ba)));
+#pragma unroll
+        for (int e = 0; e < 15; ++e) Pc[e] += (e == l) ? q : 0.0;
+      }
+      __syncthreads();
+    }
+  }
+
+  if (live && l == 0) gmemw(A.steps)[i] = steps;
+  if (inR && !live && l == 0) gmemw(A.steps)[i] = -1;
+  const auto pose = gmem(A.poses + 7 * (size_t)ic);
+  const Q q0 = qnormalize(Q{pose[3], pose[4], pose[5], pose[6]});
+  double C0[9];
+  qrot(q0, C0);
+
+  // Jacobian (:735-746): lane 0 stages F row-major in the group's LDS, the group copies it out
+  if (A.jac) {
+    if (live && l == 0) {
+#pragma unroll
+      for (int e = 0; e < 225; ++e) M[e] = (e / 15 == e % 15) ? 1.0 : 0.0;
+      double Cv[3], B[9];
+      mv3(C0, adi, Cv);
+      M[0 * 15 + 4] = Cv[2];  M[0 * 15 + 5] = -Cv[1];  // -[C_WS_0 acc_doubleintegral]x
+      M[1 * 15 + 3] = -Cv[2]; M[1 * 15 + 5] = Cv[0];
+      M[2 * 15 + 3] = Cv[1];  M[2 * 15 + 4] = -Cv[0];
+      mv3(C0, ai, Cv);
+      M[6 * 15 + 4] = Cv[2];  M[6 * 15 + 5] = -Cv[1];  // -[C_WS_0 acc_integral]x
+      M[7 * 15 + 3] = -Cv[2]; M[7 * 15 + 5] = Cv[0];
+      M[8 * 15 + 3] = Cv[1];  M[8 * 15 + 4] = -Cv[0];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) M[r * 15 + 6 + r] = Dt;
+      mm3(C0, dpdbg, B);
+#pragma unroll
+      for (int e = 0; e < 9; ++e) M[(e / 3) * 15 + 9 + e % 3] = B[e];
+      mm3(C0, Cdi, B);
+#pragma unroll
+      for (int e = 0; e < 9; ++e) M[(e / 3) * 15 + 12 + e % 3] = -B[e];
+      mm3(C0, dadbg, B);
+#pragma unroll
+      for (int e = 0; e < 9; ++e) M[(3 + e / 3) * 15 + 9 + e % 3] = -B[e];
+      mm3(C0, dvdbg, B);
+#pragma unroll
+      for (int e = 0; e < 9; ++e) M[(6 + e / 3) * 15 + 9 + e % 3] = B[e];
+      mm3(C0, Ci, B);
+#pragma unroll
+      for (int e = 0; e < 9; ++e) M[(6 + e / 3) * 15 + 12 + e % 3] = -B[e];
+    }
+    __syncthreads();
+    if (live) {
+      const auto J = gmemw(A.jac + 225 * (size_t)i);
+      for (int e = l; e < 225; e += kPropGroup) J[e] = M[e];
+    }
+    __syncthreads();
+  }
+
+  // covariance (:749-757): P = T P_delta T^T, T = diag(C0, C0, C0, I, I). Column l of T P_delta,
+  // exchange, then row l of P = T (row l of T P_delta)
+  if (COV) {
+    if (live && l < 15) {
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        double o[3];
+        mv3(C0, Pc + 3 * b, o);
+        M[l * kPS + 3 * b] = o[0]; M[l * kPS + 3 * b + 1] = o[1]; M[l * kPS + 3 * b + 2] = o[2];
+      }
+#pragma unroll
+      for (int e = 9; e < 15; ++e) M[l * kPS + e] = Pc[e];
+    }
+    __syncthreads();
+    if (live && l < 15) {
+      double Mr[15];
+#pragma unroll
+      for (int e = 0; e < 15; ++e) Mr[e] = M[e * kPS + l];
+      const auto Pout = gmemw(A.cov + 225 * (size_t)i + 15 * l);
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        double o[3];
+        mv3(C0, Mr + 3 * b, o);
+        Pout[3 * b] = o[0]; Pout[3 * b + 1] = o[1]; Pout[3 * b + 2] = o[2];
+      }
+#pragma unroll
+      for (int e = 9; e < 15; ++e) Pout[e] = Mr[e];
+    }
+  }
+
+  if (live && l == 0 && steps > 0) writeState(A, i, q0, C0, v0, Dq, ai, adi, Dt);
+}
+
+void launch_imu_propagate(const ImuPropagateDev& A, hipStream_t s) {
+  if (A.n <= 0) return;
+  if (A.cov)
+    k_imu_propagate_group<true><<<(A.n + kPropPerWG - 1) / kPropPerWG, 64, 0, s>>>(A);
+  else if (A.jac)
+    k_imu_propagate_group<false><<<(A.n + kPropPerWG - 1) / kPropPerWG, 64, 0, s>>>(A);
+  else
+    k_imu_propagate_lane<<<(A.n + 63) / 64, 64, 0, s>>>(A);
+}
+
+}  // namespace okg

@@ -20,6 +20,26 @@ void launch_eval_imu_as_solved(const DevProblem& P, int mode, hipStream_t s);  /
 // ImuError::append for a batch (P: n_imu, imu_blocks {0, f, 0, f}, imu_t0 = old t1, imu_t1 = new t1,
 // imu_sbegin / imu_ts / imu_ga = appended samples, imu_par (one row), imu_state, sb[0] = biases)
 void launch_imu_append(const DevProblem& P, hipStream_t s);
+// ImuError::propagation for a batch of independent items (kernels_imu_propagate.hip;
+// okvisgpu_imu_propagate). Device arrays in the layout of okvisgpu_imu_propagate_batch; poses and sb
+// are updated in place, steps [n] is always written (-1: samples do not reach t_end, nothing else
+// of the item is written), cov / jac [n][225] row-major or nullptr. Neither: one lane per item;
+// otherwise one 16-lane group per item, the covariance recursion only with cov.
+struct ImuPropagateDev {
+  int32_t n;
+  double par[7];  // a_max, g_max, sigma_g_c, sigma_a_c, sigma_gw_c, sigma_aw_c, g
+  double* poses;
+  double* sb;
+  const int64_t* t_start;
+  const int64_t* t_end;
+  const int32_t* sbegin;
+  const int64_t* ts;
+  const double* ga;
+  double* cov;
+  double* jac;
+  int32_t* steps;
+};
+void launch_imu_propagate(const ImuPropagateDev& A, hipStream_t s);
 // host-evaluated factors: gather the evaluation points (host_in), scatter the uploaded results
 // (host_out) into the linearisation records; the host step between them is the runtime's
 void launch_host_gather(const DevProblem& P, int mode, hipStream_t s);

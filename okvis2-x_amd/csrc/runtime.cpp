@@ -217,6 +217,10 @@ struct okvisgpu_ctx {
   // counts | n_observed): likewise the context's own, outside the arena table, grown as needed
   void* covisScratch = nullptr;
   size_t covisScratchBytes = 0;
+  // okvisgpu_imu_propagate's device arrays (stamps | CSR | samples || poses | speed/biases || steps |
+  // covariance | Jacobian): likewise
+  void* propScratch = nullptr;
+  size_t propScratchBytes = 0;
 
   void fillSummaries(const std::vector<WinState>& st, okvisgpu_summary* sums) {
     if (!sums) return;
@@ -276,6 +280,7 @@ struct okvisgpu_ctx {
     if (hostOut) (void)hipHostFree(hostOut);
     if (lmScratch) (void)hipFree(lmScratch);
     if (covisScratch) (void)hipFree(covisScratch);
+    if (propScratch) (void)hipFree(propScratch);
     for (hipEvent_t e : forkEv) (void)hipEventDestroy(e);
     for (hipStream_t q : side)
       if (q) (void)hipStreamDestroy(q);
@@ -1765,6 +1770,85 @@ int okvisgpu_imu_append(okvisgpu_ctx* c, const okvisgpu_imu_append_batch* A, int
         const bool covered = s1 > s0 && A->sample_t_ns[s1 - 1] >= A->t1_new_ns[i];
         steps[i] = covered ? (int32_t)A->state[(size_t)i * kImuState + 291] : -1;
       }
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_imu_propagate(okvisgpu_ctx* c, const okvisgpu_imu_propagate_batch* A, int32_t* steps) {
+  if (!c || !A || A->n < 0) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "imu_propagate: bad arguments");
+  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "imu_propagate: call after solve_end");
+  if (A->n == 0) return OKVISGPU_OK;
+  if (!A->poses || !A->speed_biases || !A->t_start_ns || !A->t_end_ns || !A->sample_begin || !A->sample_t_ns ||
+      !A->sample_gyr_acc)
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "imu_propagate: missing arrays");
+  return guarded(c, [&]() {
+    const size_t n = (size_t)A->n;
+    if (A->sample_begin[0] != 0) throw ArgError{"imu_propagate: sample_begin must start at 0"};
+    for (size_t i = 0; i < n; ++i)
+      if (A->sample_begin[i + 1] < A->sample_begin[i]) throw ArgError{"imu_propagate: sample_begin not monotone"};
+    for (size_t i = 0; i < n; ++i) {  // the reference's assertion (ImuError.cpp:550)
+      const int32_t s0 = A->sample_begin[i];
+      if (A->sample_begin[i + 1] == s0) throw ArgError{"imu_propagate: item " + std::to_string(i) + " has no samples"};
+      if (A->sample_t_ns[s0] > A->t_start_ns[i])
+        throw ArgError{"imu_propagate: item " + std::to_string(i) + ": first sample " + std::to_string(A->sample_t_ns[s0]) +
+                       " !<= t_start " + std::to_string(A->t_start_ns[i])};
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t ns = (size_t)A->sample_begin[n];
+    // device and pinned staging share one layout: uploaded [0, upEnd), read back [downBegin, size)
+    Arena M;
+    const size_t o_t0 = M.reserve(8 * n), o_t1 = M.reserve(8 * n), o_sbeg = M.reserve(4 * (n + 1)),
+                 o_ts = M.reserve(8 * ns), o_ga = M.reserve(48 * ns), o_pose = M.reserve(56 * n), o_sb = M.reserve(72 * n);
+    const size_t upEnd = M.size, downBegin = o_pose;
+    const size_t o_steps = M.reserve(4 * n), o_cov = A->covariance ? M.reserve(1800 * n) : 0,
+                 o_jac = A->jacobian ? M.reserve(1800 * n) : 0;
+    if (M.size > c->propScratchBytes) {
+      if (c->propScratch) HIPCHK(hipFree(c->propScratch));
+      c->propScratch = nullptr;
+      c->propScratchBytes = 0;
+      HIPCHK(hipMalloc(&c->propScratch, M.size));
+      c->propScratchBytes = M.size;
+    }
+    char* dev = static_cast<char*>(c->propScratch);
+    char* host = c->paramStage(M.size);
+    std::memcpy(host + o_t0, A->t_start_ns, 8 * n);
+    std::memcpy(host + o_t1, A->t_end_ns, 8 * n);
+    std::memcpy(host + o_sbeg, A->sample_begin, 4 * (n + 1));
+    std::memcpy(host + o_ts, A->sample_t_ns, 8 * ns);
+    std::memcpy(host + o_ga, A->sample_gyr_acc, 48 * ns);
+    std::memcpy(host + o_pose, A->poses, 56 * n);
+    std::memcpy(host + o_sb, A->speed_biases, 72 * n);
+    HIPCHK(hipMemcpyAsync(dev, host, upEnd, hipMemcpyHostToDevice, c->stream));
+    ImuPropagateDev D{};
+    D.n = A->n;
+    const okvisgpu_imu_params& ip = A->imu_params;
+    const double par[7] = {ip.a_max, ip.g_max, ip.sigma_g_c, ip.sigma_a_c, ip.sigma_gw_c, ip.sigma_aw_c, ip.g};
+    std::memcpy(D.par, par, sizeof(par));
+    D.poses = reinterpret_cast<double*>(dev + o_pose);
+    D.sb = reinterpret_cast<double*>(dev + o_sb);
+    D.t_start = reinterpret_cast<const int64_t*>(dev + o_t0);
+    D.t_end = reinterpret_cast<const int64_t*>(dev + o_t1);
+    D.sbegin = reinterpret_cast<const int32_t*>(dev + o_sbeg);
+    D.ts = reinterpret_cast<const int64_t*>(dev + o_ts);
+    D.ga = reinterpret_cast<const double*>(dev + o_ga);
+    D.cov = A->covariance ? reinterpret_cast<double*>(dev + o_cov) : nullptr;
+    D.jac = A->jacobian ? reinterpret_cast<double*>(dev + o_jac) : nullptr;
+    D.steps = reinterpret_cast<int32_t*>(dev + o_steps);
+    launch_imu_propagate(D, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host + downBegin, dev + downBegin, M.size - downBegin, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    // an uncovered item's rows stay the caller's (poses and speed/biases come back as they went up;
+    // the covariance and Jacobian rows of such an item were never written on the device)
+    const int32_t* st = reinterpret_cast<const int32_t*>(host + o_steps);
+    std::memcpy(A->poses, host + o_pose, 56 * n);
+    std::memcpy(A->speed_biases, host + o_sb, 72 * n);
+    for (size_t i = 0; i < n; ++i) {
+      if (st[i] < 0) continue;
+      if (A->covariance) std::memcpy(A->covariance + 225 * i, host + o_cov + 1800 * i, 1800);
+      if (A->jacobian) std::memcpy(A->jacobian + 225 * i, host + o_jac + 1800 * i, 1800);
+    }
+    if (steps) std::memcpy(steps, st, 4 * n);
     return (int)OKVISGPU_OK;
   });
 }

@@ -188,6 +188,13 @@ class ImuAppendBatch(C.Structure):
                 ("speed_biases", _dp), ("sample_begin", _ip), ("sample_t_ns", _lp), ("sample_gyr_acc", _dp)]
 
 
+class ImuPropagateBatch(C.Structure):
+    """okvisgpu_imu_propagate_batch: ImuError::propagation for a batch of items."""
+    _fields_ = [("n", C.c_int32), ("imu_params", ImuParams), ("poses", _dp), ("speed_biases", _dp),
+                ("t_start_ns", _lp), ("t_end_ns", _lp), ("sample_begin", _ip), ("sample_t_ns", _lp),
+                ("sample_gyr_acc", _dp), ("covariance", _dp), ("jacobian", _dp)]
+
+
 class TwoPoseEdges(C.Structure):
     _fields_ = [("n_edges", C.c_int32), ("ref_pose", _dp), ("other_pose", _dp),
                 ("n_cameras", C.c_int32), ("cameras", C.POINTER(Camera)), ("extrinsics", _dp),
@@ -222,7 +229,7 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_graph_load", "okvisgpu_graph_problem", "okvisgpu_graph_ids", "okvisgpu_graph_destroy",
     "okvisgpu_graph_save", "okvisgpu_get_stats", "okvisgpu_synth_true_extrinsics", "okvisgpu_imu_append",
     "okvisgpu_eval_host", "okvisgpu_plan_window", "okvisgpu_loss_evaluate", "okvisgpu_plan_digest",
-    "okvisgpu_launch_regime", "okvisgpu_update_landmarks", "okvisgpu_covisibilities",
+    "okvisgpu_launch_regime", "okvisgpu_update_landmarks", "okvisgpu_covisibilities", "okvisgpu_imu_propagate",
 ]
 N_PHASES = 15
 
@@ -286,6 +293,7 @@ def lib():
                                            _ip, _lp, C.POINTER(C.c_uint64)]
         L.okvisgpu_launch_regime.argtypes = [C.c_int32] * 9 + [_ip]
         L.okvisgpu_imu_append.argtypes = [C.c_void_p, C.POINTER(ImuAppendBatch), _ip]
+        L.okvisgpu_imu_propagate.argtypes = [C.c_void_p, C.POINTER(ImuPropagateBatch), _ip]
         L.okvisgpu_twopose_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _dp, _dp]
         L.okvisgpu_loss_evaluate.argtypes = [C.POINTER(Loss), C.c_double, _dp]
         L.okvisgpu_update_landmarks.argtypes = [C.c_void_p, C.POINTER(LandmarkUpdate)]
@@ -491,6 +499,32 @@ def imu_append_batch(imu_params, state, t1_old, t1_new, speed_biases, sample_beg
     b.sample_t_ns = keep[4].ctypes.data_as(_lp)
     b.sample_gyr_acc = dptr(keep[5])
     return b, keep
+
+
+def imu_propagate_batch(imu_params, poses, speed_biases, t_start, t_end, sample_begin, sample_t, sample_ga,
+                        covariance=None, jacobian=None):
+    """An okvisgpu_imu_propagate_batch over numpy arrays: (struct, arrays it points into). `poses`
+    [n, 7] and `speed_biases` [n, 9] (float64, C-contiguous) are referenced, not copied (updated in
+    place), and so are `covariance` / `jacobian` [n, 15, 15] when given (None = NULL)."""
+    n = len(t_start)
+    keep = [np.ascontiguousarray(t_start, dtype=np.int64), np.ascontiguousarray(t_end, dtype=np.int64),
+            np.ascontiguousarray(sample_begin, dtype=np.int32), np.ascontiguousarray(sample_t, dtype=np.int64),
+            np.ascontiguousarray(sample_ga, dtype=np.float64).reshape(-1, 6)]
+    for a, shape in ((poses, (n, 7)), (speed_biases, (n, 9)), (covariance, (n, 15, 15)), (jacobian, (n, 15, 15))):
+        assert a is None or (a.dtype == np.float64 and a.flags["C_CONTIGUOUS"] and a.shape == shape)
+    b = ImuPropagateBatch()
+    b.n = n
+    b.imu_params = imu_params
+    b.poses, b.speed_biases = dptr(poses), dptr(speed_biases)
+    b.t_start_ns, b.t_end_ns = keep[0].ctypes.data_as(_lp), keep[1].ctypes.data_as(_lp)
+    b.sample_begin = keep[2].ctypes.data_as(_ip)
+    b.sample_t_ns = keep[3].ctypes.data_as(_lp)
+    b.sample_gyr_acc = dptr(keep[4])
+    if covariance is not None:
+        b.covariance = dptr(covariance)
+    if jacobian is not None:
+        b.jacobian = dptr(jacobian)
+    return b, keep + [poses, speed_biases, covariance, jacobian]
 
 
 class TwoPoseBatch:
@@ -730,6 +764,24 @@ class Context:
         steps = np.zeros(b.n, dtype=np.int32)
         self._check(lib().okvisgpu_imu_append(self.h, C.byref(b), steps.ctypes.data_as(_ip)), "okvisgpu_imu_append")
         return steps
+
+    def imu_propagate(self, imu_params, poses, speed_biases, t_start, t_end, sample_begin, sample_t, sample_ga,
+                      covariance=False, jacobian=False):
+        """okvisgpu_imu_propagate (ImuError::propagation for a batch): `poses` [n, 7] and `speed_biases`
+        [n, 9] are updated in place; returns the integrated steps per item (-1: samples do not reach
+        t_end, item untouched), followed by the covariance and / or the Jacobian [n, 15, 15] when
+        requested. `covariance` / `jacobian` may also be arrays to write into (rows of items with -1
+        steps keep their contents)."""
+        n = len(t_start)
+        P = np.zeros((n, 15, 15)) if covariance is True else (None if covariance is False else covariance)
+        J = np.zeros((n, 15, 15)) if jacobian is True else (None if jacobian is False else jacobian)
+        b, keep = imu_propagate_batch(imu_params, poses, speed_biases, t_start, t_end, sample_begin, sample_t,
+                                      sample_ga, P, J)
+        steps = np.zeros(n, dtype=np.int32)
+        self._check(lib().okvisgpu_imu_propagate(self.h, C.byref(b), steps.ctypes.data_as(_ip)),
+                    "okvisgpu_imu_propagate")
+        out = (steps,) + ((P,) if P is not None else ()) + ((J,) if J is not None else ())
+        return out[0] if len(out) == 1 else out
 
     def twopose_compute(self, edges: "TwoPoseBatch"):
         """TwoPoseStandardGraphError::compute for every edge of the batch: dict of DeltaX_ [n,6],
