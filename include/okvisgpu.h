@@ -417,6 +417,57 @@ typedef struct okvisgpu_twopose_edges {
 int okvisgpu_twopose_compute(okvisgpu_ctx* ctx, const okvisgpu_twopose_edges* edges, double* delta_x,
                              double* sqrt_info, double* lin_point, double* H00, double* b0);
 
+/* ---------------------------------------------------------------- calibrating pose-graph edges
+ * (An addition to ABI 6: two new entry points and a new struct; OKVISGPU_ABI_VERSION stays 6.)
+ * TwoPoseExtrinsicsGraphError (TwoPoseExtrinsicsGraphError.cpp), the edge
+ * ViGraphEstimator::convertToPoseGraphMst creates instead of the standard one with
+ * do_extrinsics: true (ViGraphEstimator.cpp:419-427, 562-571): D = 6 + 6 n_cameras residuals over
+ * the relative pose and the cameras' T_SC blocks, camera c in rows and columns 6 + 6 c .. 11 + 6 c
+ * (stayConst_ = true, the only layout the reference constructs).
+ *
+ * okvisgpu_twopose_extrinsics_compute is ::compute (:73-330) for a batch of edges, on the inputs of
+ * okvisgpu_twopose_compute; `extrinsics` are the current estimates of the T_SC blocks and become the
+ * linearisation points of the cameras the edge observes. Per observation the residual and the
+ * minimal Jacobians w.r.t. pose (other keyframe only), landmark and the camera's extrinsics; |r| > 3
+ * dropped, Cauchy corrector where obs_cauchy is set; every landmark marginalised with
+ * PseudoInverse::symmSqrt(V, 1e-7) and left out entirely when rank < 3 and its S0 depth < 2.99; then
+ * J_ = D^(1/2) E^T (rows in ascending eigenvalue order, zero rows for eigenvalues <= 1e-8 D max) and
+ * DeltaX_ = -E D^-1 E^T b0_. Outputs per edge (host, caller-owned): delta_x [D], sqrt_info (J_)
+ * [D*D] row-major, lin_point [7] (T_S0S1 once the edge has any observation from the other keyframe,
+ * else the identity), camera_seen [n_cameras] (1 once the edge has any observation of camera c,
+ * dropped or not: the reference would have set linearisationPoints_T_SC_[c]); H00 [D*D] and b0 [D]
+ * may be NULL. An unseen camera's rows and columns of H00, its columns of sqrt_info (the rows of J_
+ * belong to eigenvalues; the camera's six zero ones head the ascending list as zero rows) and its b0
+ * and delta_x entries are exactly 0. An edge's result does not depend on the batch it is in, and is the same bits on every
+ * run. n_edges = 0 and edges without landmarks are valid (all zeros, identity lin_point). Argument
+ * checks as okvisgpu_twopose_compute; n_cameras > OKVISGPU_TWOPOSE_MAX_CAMERAS returns
+ * OKVISGPU_ERR_UNSUPPORTED before anything is launched or written. */
+#define OKVISGPU_TWOPOSE_MAX_CAMERAS 6
+int okvisgpu_twopose_extrinsics_compute(okvisgpu_ctx* ctx, const okvisgpu_twopose_edges* edges, double* delta_x,
+                                        double* sqrt_info, double* lin_point, uint8_t* camera_seen, double* H00,
+                                        double* b0);
+
+/* TwoPoseExtrinsicsGraphError(Const)::EvaluateWithMinimalJacobians (:393-610, :680-860) for a batch
+ * of computed edges at given parameter values: error = DeltaX_ + [r_S0S1 - r_lin; 2 vec(q_S0S1
+ * q_lin^-1); per seen camera r_SC - r_SC,lin; 2 vec(q_SC q_SC,lin^-1)], r = J_ error. Independent of
+ * the problem set with okvisgpu_set_problems. */
+typedef struct okvisgpu_twopose_extrinsics_eval {
+  int32_t n_edges;
+  int32_t n_cameras;
+  const double* ref_pose;           /* [n_edges][7] T_WS0                                         */
+  const double* other_pose;         /* [n_edges][7] T_WS1                                         */
+  const double* extrinsics;         /* [n_cameras][7] current T_SC (shared by the edges)          */
+  const double* delta_x;            /* [n_edges][D]                                               */
+  const double* sqrt_info;          /* [n_edges][D*D] J_ row-major                                */
+  const double* lin_point;          /* [n_edges][7] linearisationPoint_T_S0S1_                    */
+  const double* lin_extrinsics;     /* [n_edges][n_cameras][7] linearisationPoints_T_SC_ (read where seen) */
+  const uint8_t* camera_seen;       /* [n_edges][n_cameras]                                       */
+} okvisgpu_twopose_extrinsics_eval;
+/* Outputs (host, caller-owned, any may be NULL): r [n][D]; minimal Jacobians, row-major: J_ref
+ * [n][D][6], J_other [n][D][6], J_extrinsics [n][n_cameras][D][6] (zero for an unseen camera). */
+int okvisgpu_twopose_extrinsics_evaluate(okvisgpu_ctx* ctx, const okvisgpu_twopose_extrinsics_eval* edges, double* r,
+                                         double* J_ref, double* J_other, double* J_extrinsics);
+
 /* ---------------------------------------------------------------- IMU-merge elimination
  * ImuError::append (ImuError.cpp:63-255) for a batch of factors on the GPU: the step of
  * ViGraphEstimator::eliminateStateByImuMerge (ViGraphEstimator.cpp:38-171) that extends the IMU

@@ -331,4 +331,43 @@ struct TwoPoseDev {
   double* out;                // [n_edges][kTwoPoseOut]
 };
 
+// TwoPoseExtrinsicsGraphError::compute (kernels_twopose_extr.hip): the same inputs (T.out unused), the
+// scratch records pass 1 leaves for pass 2 and the outputs of dimension D = 6 + 6 n_cam. The
+// outputs are zero-filled before the launch; the kernel writes only the rows and columns of the pose
+// and of the cameras the edge observes.
+constexpr int kTwoPoseMaxCam = 6;                      // OKVISGPU_TWOPOSE_MAX_CAMERAS
+constexpr int kTwoPoseMaxD = 6 + 6 * kTwoPoseMaxCam;   // 42
+constexpr int kTpxObsRec = 32;  // per observation: J0 [12] | J2 [12] | r [2] | A [6]
+constexpr int kTpxLmRec = 10;   // per landmark: V^+ packed upper [6] | b1 [3] | keep
+struct TwoPoseExtrDev {
+  TwoPoseDev in;
+  double* obs_rec;            // [n_obs][kTpxObsRec]
+  int32_t* obs_flag;          // [n_obs] bit 0 kept, bit 1 other keyframe, bits 2.. camera
+  double* lm_rec;             // [n_lm][kTpxLmRec]
+  double* delta_x;            // [n_edges][D]
+  double* sqrt_info;          // [n_edges][D*D]
+  double* lin_point;          // [n_edges][7]
+  double* H00;                // [n_edges][D*D]
+  double* b0;                 // [n_edges][D]
+  uint8_t* seen;              // [n_edges][n_cam]
+};
+
+// TwoPoseExtrinsicsGraphError(Const)::EvaluateWithMinimalJacobians for a batch of computed edges
+// (okvisgpu_twopose_extrinsics_eval on device); any output may be null.
+struct TwoPoseExtrEvalDev {
+  int32_t n_edges, n_cam;
+  const double* ref_pose;     // [n][7]
+  const double* other_pose;   // [n][7]
+  const double* extr;         // [n_cam][7]
+  const double* delta_x;      // [n][D]
+  const double* sqrt_info;    // [n][D*D]
+  const double* lin_point;    // [n][7]
+  const double* lin_extr;     // [n][n_cam][7]
+  const uint8_t* seen;        // [n][n_cam]
+  double* r;                  // [n][D]
+  double* J_ref;              // [n][D][6]
+  double* J_other;            // [n][D][6]
+  double* J_extr;             // [n][n_cam][D][6]
+};
+
 }  // namespace okg

@@ -1105,16 +1105,11 @@ __device__ __noinline__ void evalPriorsThread(const DevProblem& P, int t, int mo
   for (int e = 0; e < 36; ++e) Jq[e] = P.rp_J[36 * (size_t)k + e];
   const double* lp = P.rp_lp + 7 * (size_t)k;
   const bool relErr = P.rp_kind[k] == 1;
-  const Q q0 = qnormalize(Q{p0[3], p0[4], p0[5], p0[6]}), q1 = qnormalize(Q{p1[3], p1[4], p1[5], p1[6]});
   const Q ql = qnormalize(Q{lp[3], lp[4], lp[5], lp[6]});
   const Q qlinv = qinv(ql);
-  double C0[9];
-  qrot(q0, C0);  // C_WS0 (C_WA); C_S0W = C0^T
-  const double d01[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-  double rS[3];
-  mtv3(C0, d01, rS);  // T_S0Si.r (T_AB.r)
-  const Q q0inv = qinv(q0);
-  const Q qrel = qnormalize(qmul(q0inv, q1));  // T_S0Si.q (T_AB.q)
+  Q q0, q1, q0inv, qrel;           // qrel: T_S0Si.q (T_AB.q)
+  double C0[9], d01[3], rS[3];     // C_WS0 (C_WA), C_S0W = C0^T; rS: T_S0Si.r (T_AB.r)
+  relPoseFrame(p0, p1, q0, q1, C0, d01, rS, q0inv, qrel);
   double err[6];
   if (relErr) {  // [r_AB_meas - r_AB; 2 vec(q_AB_meas q_AB^-1)]
     const Q dq = qmul(ql, qinv(qrel));
@@ -1137,22 +1132,9 @@ __device__ __noinline__ void evalPriorsThread(const DevProblem& P, int t, int mo
   //         JerrRef = [-C_S0W, C_S0W [r_WS - r_WS0]x; 0, -B]
   // kind 1: J0 = [C_AW, -C_AW [r_WB - r_WA]x; 0, B], J1 = [-C_AW, 0; 0, -B],
   //         B = (plus(q_AB_meas q_BW) oplus(q_WA))_3x3   (signs folded into sg below)
-  double Pm[16], Om[16], B[9];
-  if (relErr) {
-    qplusM(qmul(ql, qinv(q1)), Pm);
-    qoplusM(q0, Om);
-  } else {
-    qplusM(q0inv, Pm);
-    qoplusM(qmul(q1, qlinv), Om);
-  }
-  for (int r = 0; r < 3; ++r)
-    for (int q = 0; q < 3; ++q)
-      B[r * 3 + q] = Pm[r * 4 + 0] * Om[0 * 4 + q] + Pm[r * 4 + 1] * Om[1 * 4 + q] + Pm[r * 4 + 2] * Om[2 * 4 + q] +
-                     Pm[r * 4 + 3] * Om[3 * 4 + q];
-  double X[9], CX[9];
-  crossMx(d01, X);
-  for (int r = 0; r < 3; ++r)  // C_S0W X = C0^T X
-    for (int q = 0; q < 3; ++q) CX[r * 3 + q] = C0[0 * 3 + r] * X[0 * 3 + q] + C0[1 * 3 + r] * X[1 * 3 + q] + C0[2 * 3 + r] * X[2 * 3 + q];
+  double B[9], CX[9];
+  plusOplus3(relErr ? qmul(ql, qinv(q1)) : q0inv, relErr ? q0 : qmul(q1, qlinv), B);
+  ctCrossMx(C0, d01, CX);  // C_S0W [d01]x
   for (int r = 0; r < 6; ++r) {
     const double* Jr = Jq + r * 6;
     double* Lr = lin + 6 + r * 12;

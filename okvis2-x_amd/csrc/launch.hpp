@@ -82,7 +82,10 @@ void launch_select_current(const DevProblem& P, hipStream_t s);  // set 1 -> set
 
 // pose-graph edges (kernels_twopose.hip): TwoPoseStandardGraphError::compute, one wavefront per edge
 void launch_twopose_compute(const TwoPoseDev& T, hipStream_t s);
-
+// calibrating pose-graph edges (kernels_twopose_extr.hip): TwoPoseExtrinsicsGraphError::compute and
+// ::EvaluateWithMinimalJacobians, one workgroup per edge
+void launch_twopose_extr_compute(const TwoPoseExtrDev& T, hipStream_t s);
+void launch_twopose_extr_eval(const TwoPoseExtrEvalDev& T, hipStream_t s);
 
 // post-solve landmark pass (kernels_landmarks.hip): ViGraph::updateLandmarks on parameter set 0 (run
 // launch_select_current first), one lane per landmark. Outputs in device order: quality [n_lm],

@@ -431,6 +431,38 @@ OKG_HD void obsCore(const Cam& cam, const double L[4], const double m[2], const 
       A[rr * 3 + c] = (B[rr * 3 + 0] * C_WS[c * 3 + 0] + B[rr * 3 + 1] * C_WS[c * 3 + 1] + B[rr * 3 + 2] * C_WS[c * 3 + 2]) * sc;
 }
 
+// Pieces of the pose-graph edges' EvaluateWithMinimalJacobians (TwoPoseGraphError.cpp:467-606,
+// TwoPoseExtrinsicsGraphError.cpp:393-610, RelativePoseError.cpp:59-140), shared by k_eval_prior and
+// k_twopose_extr_eval. relPoseFrame: the normalised rotations of T_WS0 (p0) and T_WSi (p1), C0 =
+// C_WS0, d01 = r_WSi - r_WS0 and T_S0Si = T_WS0^-1 T_WSi as (rS, qrel).
+OKG_HD void relPoseFrame(const double* p0, const double* p1, Q& q0, Q& q1, double C0[9], double d01[3], double rS[3],
+                         Q& q0inv, Q& qrel) {
+  q0 = qnormalize(Q{p0[3], p0[4], p0[5], p0[6]});
+  q1 = qnormalize(Q{p1[3], p1[4], p1[5], p1[6]});
+  qrot(q0, C0);
+  d01[0] = p1[0] - p0[0]; d01[1] = p1[1] - p0[1]; d01[2] = p1[2] - p0[2];
+  mtv3(C0, d01, rS);
+  q0inv = qinv(q0);
+  qrel = qnormalize(qmul(q0inv, q1));
+}
+// B = (plus(a) oplus(b)).topLeftCorner<3,3>()
+OKG_HD void plusOplus3(const Q& a, const Q& b, double B[9]) {
+  double Pm[16], Om[16];
+  qplusM(a, Pm);
+  qoplusM(b, Om);
+  for (int r = 0; r < 3; ++r)
+    for (int q = 0; q < 3; ++q)
+      B[r * 3 + q] = Pm[r * 4 + 0] * Om[0 * 4 + q] + Pm[r * 4 + 1] * Om[1 * 4 + q] + Pm[r * 4 + 2] * Om[2 * 4 + q] +
+                     Pm[r * 4 + 3] * Om[3 * 4 + q];
+}
+// CX = C0^T [d]x
+OKG_HD void ctCrossMx(const double C0[9], const double d[3], double CX[9]) {
+  double X[9];
+  crossMx(d, X);
+  for (int r = 0; r < 3; ++r)
+    for (int q = 0; q < 3; ++q) CX[r * 3 + q] = C0[0 * 3 + r] * X[0 * 3 + q] + C0[1 * 3 + r] * X[1 * 3 + q] + C0[2 * 3 + r] * X[2 * 3 + q];
+}
+
 // Symmetric eigen-decomposition A = V diag(lam) V^T by cyclic Jacobi (Eigen's
 // SelfAdjointEigenSolver restated; eigenvalues ascending, eigenvector signs arbitrary). A is
 // destroyed. N <= 6, one thread.

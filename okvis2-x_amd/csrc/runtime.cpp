@@ -1875,6 +1875,92 @@ int okvisgpu_covisibilities(okvisgpu_ctx* c, okvisgpu_covisibility* out) {
   });
 }
 
+// An okvisgpu_twopose_edges batch checked and uploaded (okvisgpu_twopose_compute and
+// okvisgpu_twopose_extrinsics_compute): one device allocation for the inputs and for whatever `more`
+// reserves after them; T.out stays null. Throws ArgError with `who` in front.
+struct TwoPoseUpload {
+  std::unique_ptr<char, void (*)(char*)> mem{nullptr, [](char* p) { (void)hipFree(p); }};
+  TwoPoseDev T{};
+  int nl = 0, no = 0;
+};
+static void uploadTwoPose(okvisgpu_ctx* c, const okvisgpu_twopose_edges* E, const std::string& who, TwoPoseUpload& U,
+                          const std::function<void(Arena&, int, int)>& more) {
+  const int ne = E->n_edges;
+  const int nl = E->landmark_begin[ne] - E->landmark_begin[0];
+  if (E->landmark_begin[0] != 0 || nl < 0) throw ArgError{who + ": landmark_begin must start at 0"};
+  for (int e = 0; e < ne; ++e)
+    if (E->landmark_begin[e + 1] < E->landmark_begin[e]) throw ArgError{who + ": landmark_begin not monotone"};
+  const int no = nl ? E->obs_begin[nl] - E->obs_begin[0] : 0;
+  if (nl && (E->obs_begin[0] != 0 || no < 0)) throw ArgError{who + ": obs_begin must start at 0"};
+  for (int l = 0; l < nl; ++l)
+    if (E->obs_begin[l + 1] < E->obs_begin[l]) throw ArgError{who + ": obs_begin not monotone"};
+  if (no && (!E->landmarks || !E->obs_other || !E->obs_camera || !E->obs_keypoint || !E->obs_sqrt_info ||
+             !E->cameras || !E->extrinsics))
+    throw ArgError{who + ": observation arrays missing"};
+  for (int o = 0; o < no; ++o)
+    if (E->obs_camera[o] < 0 || E->obs_camera[o] >= E->n_cameras) throw ArgError{who + ": obs_camera out of range"};
+  std::vector<double> cam((size_t)kCamDoubles * std::max(1, E->n_cameras));
+  for (int k = 0; k < E->n_cameras; ++k) {
+    const okvisgpu_camera& q = E->cameras[k];
+    if (q.distortion < 0 || q.distortion > 3) throw ArgError{who + ": unknown distortion model"};
+    const double cv[kCamDoubles] = {(double)q.distortion, q.fu, q.fv, q.cu, q.cv, q.dist[0], q.dist[1],
+                                    q.dist[2], q.dist[3], q.dist[4], q.dist[5], q.dist[6], q.dist[7]};
+    std::memcpy(&cam[kCamDoubles * (size_t)k], cv, sizeof(cv));
+  }
+  std::vector<uint8_t> cauchy(std::max(1, no), 1);
+  if (E->obs_cauchy) for (int o = 0; o < no; ++o) cauchy[o] = E->obs_cauchy[o] ? 1 : 0;
+  // one scratch allocation for inputs and outputs
+  Arena A;
+  auto put = [&](size_t bytes) { return A.reserve(bytes); };
+  const size_t o_ref = put(56 * (size_t)ne), o_oth = put(56 * (size_t)ne), o_cam = put(cam.size() * 8),
+               o_ex = put(56 * (size_t)std::max(1, E->n_cameras)), o_lb = put(4 * (size_t)(ne + 1)),
+               o_lm = put(32 * (size_t)std::max(1, nl)), o_ob = put(4 * (size_t)(nl + 1)),
+               o_oo = put((size_t)std::max(1, no)), o_oc = put(4 * (size_t)std::max(1, no)),
+               o_kp = put(16 * (size_t)std::max(1, no)), o_L = put(32 * (size_t)std::max(1, no)),
+               o_ca = put((size_t)std::max(1, no));
+  more(A, nl, no);
+  char* base = nullptr;
+  HIPCHK(hipMalloc(&base, A.size));
+  U.mem.reset(base);
+  auto up = [&](size_t off, const void* src, size_t bytes) {
+    if (bytes && src) HIPCHK(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, c->stream));
+  };
+  up(o_ref, E->ref_pose, 56 * (size_t)ne);
+  up(o_oth, E->other_pose, 56 * (size_t)ne);
+  up(o_cam, cam.data(), cam.size() * 8);
+  up(o_ex, E->extrinsics, 56 * (size_t)E->n_cameras);
+  up(o_lb, E->landmark_begin, 4 * (size_t)(ne + 1));
+  if (nl) {
+    up(o_lm, E->landmarks, 32 * (size_t)nl);
+    up(o_ob, E->obs_begin, 4 * (size_t)(nl + 1));
+  }
+  if (no) {
+    up(o_oo, E->obs_other, (size_t)no);
+    up(o_oc, E->obs_camera, 4 * (size_t)no);
+    up(o_kp, E->obs_keypoint, 16 * (size_t)no);
+    up(o_L, E->obs_sqrt_info, 32 * (size_t)no);
+    up(o_ca, cauchy.data(), (size_t)no);
+  }
+  TwoPoseDev& T = U.T;
+  T.n_edges = ne;
+  T.n_cam = E->n_cameras;
+  T.ref_pose = reinterpret_cast<const double*>(base + o_ref);
+  T.other_pose = reinterpret_cast<const double*>(base + o_oth);
+  T.cam = reinterpret_cast<const double*>(base + o_cam);
+  T.extr = reinterpret_cast<const double*>(base + o_ex);
+  T.lm_begin = reinterpret_cast<const int32_t*>(base + o_lb);
+  T.lm = reinterpret_cast<const double*>(base + o_lm);
+  T.obs_begin = reinterpret_cast<const int32_t*>(base + o_ob);
+  T.obs_other = reinterpret_cast<const uint8_t*>(base + o_oo);
+  T.obs_cam = reinterpret_cast<const int32_t*>(base + o_oc);
+  T.obs_kp = reinterpret_cast<const double*>(base + o_kp);
+  T.obs_L = reinterpret_cast<const double*>(base + o_L);
+  T.obs_cauchy = reinterpret_cast<const uint8_t*>(base + o_ca);
+  if (!nl) HIPCHK(hipMemsetAsync(base + o_ob, 0, 4, c->stream));
+  U.nl = nl;
+  U.no = no;
+}
+
 int okvisgpu_twopose_compute(okvisgpu_ctx* c, const okvisgpu_twopose_edges* E, double* delta_x, double* sqrt_info,
                              double* lin_point, double* H00, double* b0) {
   if (!c || !E || E->n_edges < 0) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "twopose_compute: bad arguments");
@@ -1884,77 +1970,11 @@ int okvisgpu_twopose_compute(okvisgpu_ctx* c, const okvisgpu_twopose_edges* E, d
   return guarded(c, [&]() {
     HIPCHK(hipSetDevice(c->device));
     const int ne = E->n_edges;
-    const int nl = E->landmark_begin[ne] - E->landmark_begin[0];
-    if (E->landmark_begin[0] != 0 || nl < 0) throw ArgError{"twopose_compute: landmark_begin must start at 0"};
-    for (int e = 0; e < ne; ++e)
-      if (E->landmark_begin[e + 1] < E->landmark_begin[e]) throw ArgError{"twopose_compute: landmark_begin not monotone"};
-    const int no = nl ? E->obs_begin[nl] - E->obs_begin[0] : 0;
-    if (nl && (E->obs_begin[0] != 0 || no < 0)) throw ArgError{"twopose_compute: obs_begin must start at 0"};
-    for (int l = 0; l < nl; ++l)
-      if (E->obs_begin[l + 1] < E->obs_begin[l]) throw ArgError{"twopose_compute: obs_begin not monotone"};
-    if (no && (!E->landmarks || !E->obs_other || !E->obs_camera || !E->obs_keypoint || !E->obs_sqrt_info ||
-               !E->cameras || !E->extrinsics))
-      throw ArgError{"twopose_compute: observation arrays missing"};
-    for (int o = 0; o < no; ++o)
-      if (E->obs_camera[o] < 0 || E->obs_camera[o] >= E->n_cameras) throw ArgError{"twopose_compute: obs_camera out of range"};
-    std::vector<double> cam((size_t)kCamDoubles * std::max(1, E->n_cameras));
-    for (int k = 0; k < E->n_cameras; ++k) {
-      const okvisgpu_camera& q = E->cameras[k];
-      if (q.distortion < 0 || q.distortion > 3) throw ArgError{"twopose_compute: unknown distortion model"};
-      const double cv[kCamDoubles] = {(double)q.distortion, q.fu, q.fv, q.cu, q.cv, q.dist[0], q.dist[1],
-                                      q.dist[2], q.dist[3], q.dist[4], q.dist[5], q.dist[6], q.dist[7]};
-      std::memcpy(&cam[kCamDoubles * (size_t)k], cv, sizeof(cv));
-    }
-    std::vector<uint8_t> cauchy(std::max(1, no), 1);
-    if (E->obs_cauchy) for (int o = 0; o < no; ++o) cauchy[o] = E->obs_cauchy[o] ? 1 : 0;
-    // one scratch allocation for inputs and outputs
-    Arena A;
-    auto put = [&](size_t bytes) { return A.reserve(bytes); };
-    const size_t o_ref = put(56 * (size_t)ne), o_oth = put(56 * (size_t)ne), o_cam = put(cam.size() * 8),
-                 o_ex = put(56 * (size_t)std::max(1, E->n_cameras)), o_lb = put(4 * (size_t)(ne + 1)),
-                 o_lm = put(32 * (size_t)std::max(1, nl)), o_ob = put(4 * (size_t)(nl + 1)),
-                 o_oo = put((size_t)std::max(1, no)), o_oc = put(4 * (size_t)std::max(1, no)),
-                 o_kp = put(16 * (size_t)std::max(1, no)), o_L = put(32 * (size_t)std::max(1, no)),
-                 o_ca = put((size_t)std::max(1, no)), o_out = put(8 * (size_t)kTwoPoseOut * ne);
-    char* base = nullptr;
-    HIPCHK(hipMalloc(&base, A.size));
-    std::unique_ptr<char, void (*)(char*)> guard(base, [](char* p) { (void)hipFree(p); });
-    auto up = [&](size_t off, const void* src, size_t bytes) {
-      if (bytes && src) HIPCHK(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, c->stream));
-    };
-    up(o_ref, E->ref_pose, 56 * (size_t)ne);
-    up(o_oth, E->other_pose, 56 * (size_t)ne);
-    up(o_cam, cam.data(), cam.size() * 8);
-    up(o_ex, E->extrinsics, 56 * (size_t)E->n_cameras);
-    up(o_lb, E->landmark_begin, 4 * (size_t)(ne + 1));
-    if (nl) {
-      up(o_lm, E->landmarks, 32 * (size_t)nl);
-      up(o_ob, E->obs_begin, 4 * (size_t)(nl + 1));
-    }
-    if (no) {
-      up(o_oo, E->obs_other, (size_t)no);
-      up(o_oc, E->obs_camera, 4 * (size_t)no);
-      up(o_kp, E->obs_keypoint, 16 * (size_t)no);
-      up(o_L, E->obs_sqrt_info, 32 * (size_t)no);
-      up(o_ca, cauchy.data(), (size_t)no);
-    }
-    TwoPoseDev T{};
-    T.n_edges = ne;
-    T.n_cam = E->n_cameras;
-    T.ref_pose = reinterpret_cast<const double*>(base + o_ref);
-    T.other_pose = reinterpret_cast<const double*>(base + o_oth);
-    T.cam = reinterpret_cast<const double*>(base + o_cam);
-    T.extr = reinterpret_cast<const double*>(base + o_ex);
-    T.lm_begin = reinterpret_cast<const int32_t*>(base + o_lb);
-    T.lm = reinterpret_cast<const double*>(base + o_lm);
-    T.obs_begin = reinterpret_cast<const int32_t*>(base + o_ob);
-    T.obs_other = reinterpret_cast<const uint8_t*>(base + o_oo);
-    T.obs_cam = reinterpret_cast<const int32_t*>(base + o_oc);
-    T.obs_kp = reinterpret_cast<const double*>(base + o_kp);
-    T.obs_L = reinterpret_cast<const double*>(base + o_L);
-    T.obs_cauchy = reinterpret_cast<const uint8_t*>(base + o_ca);
-    T.out = reinterpret_cast<double*>(base + o_out);
-    if (!nl) HIPCHK(hipMemsetAsync(base + o_ob, 0, 4, c->stream));
+    TwoPoseUpload U;
+    size_t o_out = 0;
+    uploadTwoPose(c, E, "twopose_compute", U, [&](Arena& A, int, int) { o_out = A.reserve(8 * (size_t)kTwoPoseOut * ne); });
+    TwoPoseDev& T = U.T;
+    T.out = reinterpret_cast<double*>(U.mem.get() + o_out);
     launch_twopose_compute(T, c->stream);
     HIPCHK(hipGetLastError());
     std::vector<double> out((size_t)kTwoPoseOut * ne);
@@ -1968,6 +1988,129 @@ int okvisgpu_twopose_compute(okvisgpu_ctx* c, const okvisgpu_twopose_edges* E, d
       if (H00) std::memcpy(&H00[36 * (size_t)e], r + 49, 36 * 8);
       if (b0) std::memcpy(&b0[6 * (size_t)e], r + 85, 6 * 8);
     }
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_twopose_extrinsics_compute(okvisgpu_ctx* c, const okvisgpu_twopose_edges* E, double* delta_x,
+                                        double* sqrt_info, double* lin_point, uint8_t* camera_seen, double* H00,
+                                        double* b0) {
+  if (!c || !E || E->n_edges < 0 || E->n_cameras < 0)
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "twopose_extrinsics_compute: bad arguments");
+  static_assert(kTwoPoseMaxCam == OKVISGPU_TWOPOSE_MAX_CAMERAS, "device bound and header bound differ");
+  if (E->n_cameras > OKVISGPU_TWOPOSE_MAX_CAMERAS)
+    return fail(c, OKVISGPU_ERR_UNSUPPORTED, "twopose_extrinsics_compute: more than OKVISGPU_TWOPOSE_MAX_CAMERAS cameras");
+  if (E->n_edges == 0) return OKVISGPU_OK;
+  if (!E->ref_pose || !E->other_pose || !E->landmark_begin || !E->obs_begin || !delta_x || !sqrt_info || !lin_point ||
+      (E->n_cameras && !camera_seen))
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "twopose_extrinsics_compute: missing arrays");
+  return guarded(c, [&]() {
+    HIPCHK(hipSetDevice(c->device));
+    const size_t ne = (size_t)E->n_edges, nc = (size_t)E->n_cameras, D = 6 + 6 * nc;
+    TwoPoseUpload U;
+    // scratch records of pass 1 | outputs, zero-filled: the kernel writes the observed rows only
+    size_t o_rec = 0, o_flag = 0, o_lmr = 0, o_dx = 0, o_J = 0, o_lin = 0, o_H = 0, o_b = 0, o_seen = 0, outEnd = 0;
+    uploadTwoPose(c, E, "twopose_extrinsics_compute", U, [&](Arena& A, int nl, int no) {
+      o_rec = A.reserve(8 * (size_t)kTpxObsRec * std::max(1, no));
+      o_flag = A.reserve(4 * (size_t)std::max(1, no));
+      o_lmr = A.reserve(8 * (size_t)kTpxLmRec * std::max(1, nl));
+      o_dx = A.reserve(8 * D * ne);
+      o_J = A.reserve(8 * D * D * ne);
+      o_lin = A.reserve(56 * ne);
+      o_H = A.reserve(8 * D * D * ne);
+      o_b = A.reserve(8 * D * ne);
+      o_seen = A.reserve(std::max<size_t>(1, nc * ne));
+      outEnd = A.size;
+    });
+    char* base = U.mem.get();
+    TwoPoseExtrDev X{};
+    X.in = U.T;
+    X.obs_rec = reinterpret_cast<double*>(base + o_rec);
+    X.obs_flag = reinterpret_cast<int32_t*>(base + o_flag);
+    X.lm_rec = reinterpret_cast<double*>(base + o_lmr);
+    X.delta_x = reinterpret_cast<double*>(base + o_dx);
+    X.sqrt_info = reinterpret_cast<double*>(base + o_J);
+    X.lin_point = reinterpret_cast<double*>(base + o_lin);
+    X.H00 = reinterpret_cast<double*>(base + o_H);
+    X.b0 = reinterpret_cast<double*>(base + o_b);
+    X.seen = reinterpret_cast<uint8_t*>(base + o_seen);
+    HIPCHK(hipMemsetAsync(base + o_dx, 0, outEnd - o_dx, c->stream));
+    launch_twopose_extr_compute(X, c->stream);
+    HIPCHK(hipGetLastError());
+    std::vector<char> out(outEnd - o_dx);
+    HIPCHK(hipMemcpyAsync(out.data(), base + o_dx, out.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    auto down = [&](void* dst, size_t off, size_t bytes) {
+      if (dst && bytes) std::memcpy(dst, out.data() + (off - o_dx), bytes);
+    };
+    down(delta_x, o_dx, 8 * D * ne);
+    down(sqrt_info, o_J, 8 * D * D * ne);
+    down(lin_point, o_lin, 56 * ne);
+    down(H00, o_H, 8 * D * D * ne);
+    down(b0, o_b, 8 * D * ne);
+    down(camera_seen, o_seen, nc * ne);
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_twopose_extrinsics_evaluate(okvisgpu_ctx* c, const okvisgpu_twopose_extrinsics_eval* V, double* r,
+                                         double* J_ref, double* J_other, double* J_extrinsics) {
+  if (!c || !V || V->n_edges < 0 || V->n_cameras < 0)
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "twopose_extrinsics_evaluate: bad arguments");
+  if (V->n_cameras > OKVISGPU_TWOPOSE_MAX_CAMERAS)
+    return fail(c, OKVISGPU_ERR_UNSUPPORTED, "twopose_extrinsics_evaluate: more than OKVISGPU_TWOPOSE_MAX_CAMERAS cameras");
+  if (V->n_edges == 0) return OKVISGPU_OK;
+  if (!V->ref_pose || !V->other_pose || !V->delta_x || !V->sqrt_info || !V->lin_point ||
+      (V->n_cameras && (!V->extrinsics || !V->lin_extrinsics || !V->camera_seen)))
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "twopose_extrinsics_evaluate: missing arrays");
+  return guarded(c, [&]() {
+    HIPCHK(hipSetDevice(c->device));
+    const size_t ne = (size_t)V->n_edges, nc = (size_t)V->n_cameras, D = 6 + 6 * nc;
+    Arena A;
+    const size_t o_ref = A.reserve(56 * ne), o_oth = A.reserve(56 * ne), o_ex = A.reserve(56 * nc),
+                 o_dx = A.reserve(8 * D * ne), o_J = A.reserve(8 * D * D * ne), o_lin = A.reserve(56 * ne),
+                 o_lex = A.reserve(56 * nc * ne), o_seen = A.reserve(nc * ne);
+    const size_t o_r = r ? A.reserve(8 * D * ne) : 0, o_jr = J_ref ? A.reserve(48 * D * ne) : 0,
+                 o_jo = J_other ? A.reserve(48 * D * ne) : 0, o_je = J_extrinsics ? A.reserve(48 * D * nc * ne) : 0;
+    char* base = nullptr;
+    HIPCHK(hipMalloc(&base, A.size));
+    std::unique_ptr<char, void (*)(char*)> guard(base, [](char* p) { (void)hipFree(p); });
+    auto up = [&](size_t off, const void* src, size_t bytes) {
+      if (bytes && src) HIPCHK(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, c->stream));
+    };
+    up(o_ref, V->ref_pose, 56 * ne);
+    up(o_oth, V->other_pose, 56 * ne);
+    up(o_ex, V->extrinsics, 56 * nc);
+    up(o_dx, V->delta_x, 8 * D * ne);
+    up(o_J, V->sqrt_info, 8 * D * D * ne);
+    up(o_lin, V->lin_point, 56 * ne);
+    up(o_lex, V->lin_extrinsics, 56 * nc * ne);
+    up(o_seen, V->camera_seen, nc * ne);
+    TwoPoseExtrEvalDev T{};
+    T.n_edges = V->n_edges;
+    T.n_cam = V->n_cameras;
+    T.ref_pose = reinterpret_cast<const double*>(base + o_ref);
+    T.other_pose = reinterpret_cast<const double*>(base + o_oth);
+    T.extr = reinterpret_cast<const double*>(base + o_ex);
+    T.delta_x = reinterpret_cast<const double*>(base + o_dx);
+    T.sqrt_info = reinterpret_cast<const double*>(base + o_J);
+    T.lin_point = reinterpret_cast<const double*>(base + o_lin);
+    T.lin_extr = reinterpret_cast<const double*>(base + o_lex);
+    T.seen = reinterpret_cast<const uint8_t*>(base + o_seen);
+    T.r = r ? reinterpret_cast<double*>(base + o_r) : nullptr;
+    T.J_ref = J_ref ? reinterpret_cast<double*>(base + o_jr) : nullptr;
+    T.J_other = J_other ? reinterpret_cast<double*>(base + o_jo) : nullptr;
+    T.J_extr = J_extrinsics ? reinterpret_cast<double*>(base + o_je) : nullptr;
+    launch_twopose_extr_eval(T, c->stream);
+    HIPCHK(hipGetLastError());
+    auto down = [&](double* dst, const double* src, size_t bytes) {
+      if (dst && bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    };
+    down(r, T.r, 8 * D * ne);
+    down(J_ref, T.J_ref, 48 * D * ne);
+    down(J_other, T.J_other, 48 * D * ne);
+    down(J_extrinsics, T.J_extr, 48 * D * nc * ne);
+    HIPCHK(hipStreamSynchronize(c->stream));
     return (int)OKVISGPU_OK;
   });
 }

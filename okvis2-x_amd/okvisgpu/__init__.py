@@ -202,6 +202,13 @@ class TwoPoseEdges(C.Structure):
                 ("obs_camera", _ip), ("obs_keypoint", _dp), ("obs_sqrt_info", _dp), ("obs_cauchy", _up)]
 
 
+class TwoPoseExtrinsicsEval(C.Structure):
+    """okvisgpu_twopose_extrinsics_eval: computed calibrating edges and the values to evaluate them at."""
+    _fields_ = [("n_edges", C.c_int32), ("n_cameras", C.c_int32), ("ref_pose", _dp), ("other_pose", _dp),
+                ("extrinsics", _dp), ("delta_x", _dp), ("sqrt_info", _dp), ("lin_point", _dp),
+                ("lin_extrinsics", _dp), ("camera_seen", _up)]
+
+
 class LandmarkUpdate(C.Structure):
     """okvisgpu_landmark_update: one window's outputs of okvisgpu_update_landmarks."""
     _fields_ = [("quality", _dp), ("initialised", _up), ("reset", _up), ("obs_error", _dp),
@@ -230,8 +237,10 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_graph_save", "okvisgpu_get_stats", "okvisgpu_synth_true_extrinsics", "okvisgpu_imu_append",
     "okvisgpu_eval_host", "okvisgpu_plan_window", "okvisgpu_loss_evaluate", "okvisgpu_plan_digest",
     "okvisgpu_launch_regime", "okvisgpu_update_landmarks", "okvisgpu_covisibilities", "okvisgpu_imu_propagate",
+    "okvisgpu_twopose_extrinsics_compute", "okvisgpu_twopose_extrinsics_evaluate",
 ]
 N_PHASES = 15
+TWOPOSE_MAX_CAMERAS = 6
 
 _lib = None
 
@@ -295,6 +304,10 @@ def lib():
         L.okvisgpu_imu_append.argtypes = [C.c_void_p, C.POINTER(ImuAppendBatch), _ip]
         L.okvisgpu_imu_propagate.argtypes = [C.c_void_p, C.POINTER(ImuPropagateBatch), _ip]
         L.okvisgpu_twopose_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _dp, _dp]
+        L.okvisgpu_twopose_extrinsics_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _up, _dp,
+                                                          _dp]
+        L.okvisgpu_twopose_extrinsics_evaluate.argtypes = [C.c_void_p, C.POINTER(TwoPoseExtrinsicsEval), _dp, _dp, _dp,
+                                                           _dp]
         L.okvisgpu_loss_evaluate.argtypes = [C.POINTER(Loss), C.c_double, _dp]
         L.okvisgpu_update_landmarks.argtypes = [C.c_void_p, C.POINTER(LandmarkUpdate)]
         L.okvisgpu_covisibilities.argtypes = [C.c_void_p, C.POINTER(Covisibility)]
@@ -792,6 +805,51 @@ class Context:
         self._check(lib().okvisgpu_twopose_compute(self.h, C.byref(edges.struct), dptr(out["delta_x"]),
                                                    dptr(out["sqrt_info"]), dptr(out["lin_point"]), dptr(out["H00"]),
                                                    dptr(out["b0"])), "okvisgpu_twopose_compute")
+        return out
+
+    def twopose_extrinsics_compute(self, edges: "TwoPoseBatch", out=None):
+        """TwoPoseExtrinsicsGraphError::compute (the edge of do_extrinsics: true) for every edge of the
+        batch, D = 6 + 6 n_cameras: dict of DeltaX_ [n,D], J_ [n,D,D], linearisation point [n,7],
+        camera_seen [n,C] (uint8), H00_ [n,D,D], b0_ [n,D]. `out` may be such a dict to write into."""
+        n, nc = edges.struct.n_edges, edges.struct.n_cameras
+        D = 6 + 6 * nc
+        if out is None:
+            out = {"delta_x": np.zeros((n, D)), "sqrt_info": np.zeros((n, D, D)), "lin_point": np.zeros((n, 7)),
+                   "camera_seen": np.zeros((n, nc), dtype=np.uint8), "H00": np.zeros((n, D, D)), "b0": np.zeros((n, D))}
+        self._check(lib().okvisgpu_twopose_extrinsics_compute(
+            self.h, C.byref(edges.struct), dptr(out["delta_x"]), dptr(out["sqrt_info"]), dptr(out["lin_point"]),
+            out["camera_seen"].ctypes.data_as(_up), dptr(out["H00"]), dptr(out["b0"])),
+            "okvisgpu_twopose_extrinsics_compute")
+        return out
+
+    def twopose_extrinsics_evaluate(self, ref_pose, other_pose, extrinsics, edges, lin_extrinsics,
+                                    want=("r", "J_ref", "J_other", "J_extrinsics")):
+        """TwoPoseExtrinsicsGraphError::EvaluateWithMinimalJacobians for a batch of computed edges.
+        ref_pose / other_pose [n,7] and extrinsics [C,7] are the values to evaluate at, `edges` the dict
+        twopose_extrinsics_compute returned, lin_extrinsics [n,C,7] (or [C,7] for all edges) the
+        extrinsics the edges were computed with. Returns a dict of the outputs named in `want`:
+        r [n,D], J_ref / J_other [n,D,6], J_extrinsics [n,C,D,6] (minimal, row-major)."""
+        ref = np.ascontiguousarray(ref_pose, dtype=np.float64).reshape(-1, 7)
+        oth = np.ascontiguousarray(other_pose, dtype=np.float64).reshape(-1, 7)
+        ex = np.ascontiguousarray(extrinsics, dtype=np.float64).reshape(-1, 7)
+        n, nc = len(ref), len(ex)
+        D = 6 + 6 * nc
+        lex = np.asarray(lin_extrinsics, dtype=np.float64)
+        lex = np.ascontiguousarray(np.broadcast_to(lex.reshape(-1, nc, 7) if nc else lex.reshape(-1, 0, 7), (n, nc, 7)))
+        dx = np.ascontiguousarray(edges["delta_x"], dtype=np.float64).reshape(n, D)
+        J = np.ascontiguousarray(edges["sqrt_info"], dtype=np.float64).reshape(n, D, D)
+        lin = np.ascontiguousarray(edges["lin_point"], dtype=np.float64).reshape(n, 7)
+        seen = np.ascontiguousarray(edges["camera_seen"], dtype=np.uint8).reshape(n, nc)
+        s = TwoPoseExtrinsicsEval()
+        s.n_edges, s.n_cameras = n, nc
+        s.ref_pose, s.other_pose, s.extrinsics = dptr(ref), dptr(oth), dptr(ex)
+        s.delta_x, s.sqrt_info, s.lin_point, s.lin_extrinsics = dptr(dx), dptr(J), dptr(lin), dptr(lex)
+        s.camera_seen = seen.ctypes.data_as(_up)
+        shapes = {"r": (n, D), "J_ref": (n, D, 6), "J_other": (n, D, 6), "J_extrinsics": (n, nc, D, 6)}
+        out = {k: np.zeros(shapes[k]) for k in want}
+        ptr = [dptr(out[k]) if k in out else None for k in ("r", "J_ref", "J_other", "J_extrinsics")]
+        self._check(lib().okvisgpu_twopose_extrinsics_evaluate(self.h, C.byref(s), *ptr),
+                    "okvisgpu_twopose_extrinsics_evaluate")
         return out
 
     def update_landmarks(self, n_windows: Optional[int] = None):
