@@ -683,6 +683,29 @@ int okvisgpu_evaluate(okvisgpu_ctx* ctx, int32_t window, double* cost);
 int okvisgpu_linearize_reduce(okvisgpu_ctx* ctx, int32_t window, int32_t jacobi_scaling, double mu,
                               double* S, double* rhs, double* cost, int32_t* dim_out);
 
+/* Development (a test hook, not part of the drop-in boundary): one Gauss-Newton solution of window w
+ * at the current parameters, as the first iteration of a solve forms it. Of `options` (NULL: the
+ * defaults) jacobi_scaling, cholesky_schedule, min_lm_diagonal and max_lm_diagonal apply; the rest
+ * is ignored. The whole resident batch is linearised at the damping mu, reduced, factorised and
+ * back-substituted (GN prep, assembly, Cholesky, landmark back substitution); two vectors of
+ * window w come back (host, either may be NULL):
+ *   y_f [dim]             the solution of S y_f = rhs, S and rhs being what
+ *                         okvisgpu_linearize_reduce(ctx, w, jacobi_scaling, mu, ...) returns with the
+ *                         same LM diagonal bounds, in its reduced ordering. y_f is in the
+ *                         Jacobi-scaled space; DoglegStrategy's gauss_newton_step_ is -D y_f
+ *                         (D = diagonal_, the dogleg scaling).
+ *   y_l [3 * n_landmarks] per landmark, in the caller's order, zero for a constant landmark:
+ *                         y_l = V'^-1 (s g_l - s W^T s_p y_p), V' the landmark's scaled and damped
+ *                         3x3 block, s / s_p the Jacobi scales of the landmark / its poses, W its
+ *                         pose-landmark blocks and y_p the poses' (and variable extrinsics') rows of
+ *                         y_f; gauss_newton_step_ = -D y_l.
+ * dim_out [1] receives the reduced dimension. Returns OKVISGPU_ERR_NUMERICAL when the step of window
+ * w failed (a landmark block or a pivot of S not positive definite at this mu: a solve would retry
+ * with a larger mu); the outputs are then untouched. Not callable between okvisgpu_solve_begin and
+ * okvisgpu_solve_end; the solve state is scratch afterwards, as after okvisgpu_linearize_reduce. */
+int okvisgpu_gauss_newton_step(okvisgpu_ctx* ctx, int32_t window, const okvisgpu_options* options,
+                               double mu, double* y_f, double* y_l, int32_t* dim_out);
+
 /* Raw per-residual evaluation for parity tests (EvaluateWithMinimalJacobians semantics, no loss):
  *   reprojection: r [n_obs][2], J_pose [n_obs][2][6], J_landmark [n_obs][2][3] (minimal, row-major)
  *   imu:          r [n_imu][15], J [n_imu][15][30] minimal columns (pose0 6, sb0 9, pose1 6, sb1 9)

@@ -1528,6 +1528,10 @@ int okvisgpu_plan_window(const okvisgpu_problem* p, int32_t nested_dissection, i
     if (natural)
       for (int r = 0; r < fpad; ++r) natural[r] = r < B.win_fdim[0] ? B.f_nat[r] : -1;
     return OKVISGPU_OK;
+  } catch (const UnsupportedError&) {
+    return OKVISGPU_ERR_UNSUPPORTED;
+  } catch (const ArgError&) {  // (a bad problem: as okvisgpu_plan_digest reports it)
+    return OKVISGPU_ERR_INVALID_ARGUMENT;
   } catch (const std::exception&) {
     return OKVISGPU_ERR_INVALID_ARGUMENT;
   }
@@ -1598,6 +1602,60 @@ int okvisgpu_linearize_reduce(okvisgpu_ctx* c, int32_t window, int32_t jacobi_sc
         if (nat[r] >= 0) rhs[nat[r]] = v[r];
     }
     if (st[window].gn_failed) return fail(c, OKVISGPU_ERR_NUMERICAL, "landmark block not positive definite");
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_gauss_newton_step(okvisgpu_ctx* c, int32_t window, const okvisgpu_options* options, double mu,
+                               double* y_f, double* y_l, int32_t* dim_out) {
+  if (!c) return OKVISGPU_ERR_INVALID_ARGUMENT;
+  if (!c->haveProblem) return fail(c, OKVISGPU_ERR_NO_PROBLEM, "no problem set");
+  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "gauss_newton_step: call after solve_end");
+  if (window < 0 || window >= c->P.n_win) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "bad window");
+  return guarded(c, [&]() {
+    HIPCHK(hipSetDevice(c->device));
+    okvisgpu_options o;
+    okvisgpu_default_options(&o);
+    if (options) {
+      o.jacobi_scaling = options->jacobi_scaling;
+      o.cholesky_schedule = options->cholesky_schedule;
+      o.min_lm_diagonal = options->min_lm_diagonal;
+      o.max_lm_diagonal = options->max_lm_diagonal;
+    }
+    c->setOptions(o);
+    c->resetStates(mu);
+    c->ensureS(c->stream);
+    c->launchInit(2);
+    // the first iteration's Gauss-Newton solve (unfusedSteps), over the whole resident batch
+    launch_lm_prep(c->P, c->stream);
+    launch_assemble(c->P, c->stream);
+    launch_cholesky(c->P, c->stream);
+    launch_lm_backsub(c->P, c->stream);
+    HIPCHK(hipGetLastError());
+    auto st = c->readStates();
+    const HostBatch& B = c->B;
+    const int fdim = B.win_fdim[window], dn = B.win_fnat[window];
+    if (dim_out) *dim_out = dn;
+    if (st[window].dev_error)
+      throw HipError{"window " + std::to_string(window) + ": the pipelined Cholesky's team wait reached its limit",
+                     OKVISGPU_ERR_DEVICE};
+    if (st[window].gn_failed) return fail(c, OKVISGPU_ERR_NUMERICAL, "Gauss-Newton step: a block is not positive definite");
+    if (y_f && dn) {  // natural order, as okvisgpu_linearize_reduce exports rhs
+      const int32_t* nat = B.f_nat.data() + B.win_foff[window];
+      std::vector<double> v(fdim);
+      HIPCHK(hipMemcpy(v.data(), c->P.yF + B.win_foff[window], sizeof(double) * fdim, hipMemcpyDeviceToHost));
+      for (int r = 0; r < fdim; ++r)
+        if (nat[r] >= 0) y_f[nat[r]] = v[r];
+    }
+    const int nl = c->probs[window]->n_landmarks;
+    if (y_l && nl) {  // the caller's landmark order
+      const int lb = B.lm_base[window];
+      const int* perm = &B.lm_perm[lb];
+      std::vector<double> v(3 * (size_t)nl);
+      HIPCHK(hipMemcpy(v.data(), c->P.yL + 3 * (size_t)lb, sizeof(double) * v.size(), hipMemcpyDeviceToHost));
+      for (int k = 0; k < nl; ++k)
+        for (int a = 0; a < 3; ++a) y_l[3 * (size_t)perm[k] + a] = B.lm_free[lb + k] ? v[3 * (size_t)k + a] : 0.0;
+    }
     return (int)OKVISGPU_OK;
   });
 }

@@ -237,7 +237,7 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_graph_save", "okvisgpu_get_stats", "okvisgpu_synth_true_extrinsics", "okvisgpu_imu_append",
     "okvisgpu_eval_host", "okvisgpu_plan_window", "okvisgpu_loss_evaluate", "okvisgpu_plan_digest",
     "okvisgpu_launch_regime", "okvisgpu_update_landmarks", "okvisgpu_covisibilities", "okvisgpu_imu_propagate",
-    "okvisgpu_twopose_extrinsics_compute", "okvisgpu_twopose_extrinsics_evaluate",
+    "okvisgpu_twopose_extrinsics_compute", "okvisgpu_twopose_extrinsics_evaluate", "okvisgpu_gauss_newton_step",
 ]
 N_PHASES = 15
 TWOPOSE_MAX_CAMERAS = 6
@@ -266,6 +266,7 @@ def lib():
         L.okvisgpu_get_params.argtypes = [C.c_void_p]
         L.okvisgpu_evaluate.argtypes = [C.c_void_p, C.c_int32, _dp]
         L.okvisgpu_linearize_reduce.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, _dp, _dp, _dp, _ip]
+        L.okvisgpu_gauss_newton_step.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Options), C.c_double, _dp, _dp, _ip]
         L.okvisgpu_eval_reprojection.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp]
         L.okvisgpu_eval_imu.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]
         L.okvisgpu_synth_default_config.argtypes = [C.POINTER(SynthConfig), C.c_int32, C.c_int32, C.c_int32, C.c_uint64]
@@ -740,6 +741,23 @@ class Context:
         self._check(lib().okvisgpu_linearize_reduce(self.h, window, int(jacobi_scaling), mu, dptr(S), dptr(rhs),
                                                      C.byref(cost), C.byref(dim)), "linearize_reduce")
         return S, rhs, cost.value
+
+    def gauss_newton_step(self, window=0, options: Optional[Options] = None, mu=0.0):
+        """okvisgpu_gauss_newton_step (development): (y_f [dim], y_l [n_landmarks, 3]) of one Gauss-Newton
+        solve of `window` at the current parameters: y_f solves the system linearize_reduce(window,
+        options.jacobi_scaling, mu) returns, y_l are the landmarks' back-substituted steps in the
+        caller's order. Raises OkvisGpuError (status OKVISGPU_ERR_NUMERICAL) when the step failed."""
+        if self._keep is None:
+            raise OkvisGpuError("no problem set")
+        o = C.byref(options) if options is not None else None
+        dim = C.c_int32()
+        self._check(lib().okvisgpu_gauss_newton_step(self.h, window, o, mu, None, None, C.byref(dim)),
+                    "gauss_newton_step(dim)")
+        y_f = np.zeros(dim.value)
+        y_l = np.zeros((self._keep[1][window].n_landmarks, 3))
+        self._check(lib().okvisgpu_gauss_newton_step(self.h, window, o, mu, dptr(y_f), dptr(y_l), C.byref(dim)),
+                    "gauss_newton_step")
+        return y_f, y_l
 
     def eval_reprojection(self, n_obs, window=0):
         r = np.zeros((n_obs, 2))

@@ -99,3 +99,14 @@ def test_nested_dissection_full_graph(og):
     assert r["launches"] <= r0["launches"]
     if r["split_tS"]:
         assert not r["tile_nz"][r["split_tL"]:r["split_tS"], :r["split_tL"]].any()
+
+
+def test_bad_problem_is_an_error(og):
+    """A problem the planner rejects comes back as a status (as from okvisgpu_plan_digest), not as an
+    exception leaving the C boundary."""
+    from _problem import OwnedProblem
+    P = OwnedProblem.copy_of(og.SynthWindow(4, 160, 1200, seed=7).problem)
+    P.obs_pose[3] = len(P.poses)
+    P.bind()
+    with pytest.raises(RuntimeError, match="okvisgpu_plan_window failed"):
+        og.plan_window(P.struct, 1)
