@@ -528,6 +528,114 @@ typedef struct okvisgpu_imu_propagate_batch {
 } okvisgpu_imu_propagate_batch;
 int okvisgpu_imu_propagate(okvisgpu_ctx* ctx, const okvisgpu_imu_propagate_batch* batch, int32_t* steps);
 
+/* ---------------------------------------------------------------- map matching
+ * (An addition to ABI 6: a new entry point and two new structs; OKVISGPU_ABI_VERSION stays 6.)
+ * The matching of Frontend::matchToMap (okvis_frontend/src/Frontend.cpp:1299-1741) on the GPU: the
+ * candidate preparation of :1335-1508 and the two matching passes, matchToMapByThread (:1745-1827)
+ * and matchToMapByThreadUnitialised (:1831-1956, with triangulateFast, stereo_triangulation.cpp:30-112).
+ * One batch is one map shared by n_jobs jobs; a job is one camera image of the current frame in one
+ * pass (0: the initialised-landmark pass, 1: the uninitialised pass). Landmarks are in ascending
+ * LandmarkId order and each landmark's observations in std::set<KeypointIdentifier> order (ascending
+ * frame, camera, keypoint): the iteration orders of the reference's maps; observations are walked
+ * backwards, as rbegin() does. normalised(v) below is v / |v| for |v|^2 > 0 and v otherwise (Eigen).
+ *
+ * Candidates, per job and landmark passing landmark_use: T_WC1 = pose_prepare T_SC[camera], p_W =
+ * hp.xyz / hp.w, r_W = p_W - r_WC1, e_W = normalised(r_W), r = max(0.01, |r_W|). The landmark is
+ * skipped when projectHomogeneous(T_WC1^-1 hp_W) is Invalid (|z| < 1e-12; radtan8 with rho > 9) or
+ * Behind (inside the image and z <= 0: a point behind the camera that projects outside the image is not
+ * skipped; no mask), or lies more than reprThreshold = 3 + f (imu_use ? 0.06 : 0.34), f = (fu + fv) / 2,
+ * outside [0, width] x [0, height]. Per observation, newest first, with F = fu + fv (the sum here, the
+ * mean elsewhere, as in the reference), T_WC_old = T_WS[obs_pose] T_SC[obs_camera] and r_old = p_W -
+ * r_WC_old: while the landmark is not yet 3D it becomes 3D if normalised(r_W) . normalised(r_W -
+ * (0.2 / F / quality) r_old) > cos(10 / F) (plain IEEE arithmetic: quality 0 gives NaN and the
+ * landmark stays not-3D); unless loop_closure the observation is skipped if cosV = e_W .
+ * normalised(r_old) < cos(0.6) or scaleChange = |r - |r_old|| / r > 0.5; score = 0.5 (acos(cosV) / 0.6 +
+ * scaleChange / 0.5). Three slots start at score 1.0; the slot to replace is the first holding the
+ * strictly largest score (the scan starting from 0.0), and the observation is stored there only if its
+ * score is below that slot's; a slot keeps the descriptor, e0_W = C_WC_old normalised(obs_ray) and
+ * r0_W = r_WC_old.
+ * Deviation: a landmark without a stored slot is left out (cand_n = -1); the reference keeps one row
+ * of uninitialised descriptor-pool memory for it (:1488).
+ *
+ * Pass 0: a keypoint takes part unless it carries a landmark and loop_closure is 0. It walks the 3D
+ * candidates in landmark order and within a landmark in slot order; a landmark is skipped when
+ * |projection - keypoint|^2 > reprThreshold^2; a candidate is a record iff its Hamming distance over
+ * the 48 bytes is < best (as doubles; best starts at matching_threshold and then holds the last
+ * record's distance). A record sets the match, adds 1 to n_records and the reprojection distance to
+ * record_repr_sum.
+ * Pass 1: T_WC1 from pose_match, sigma = 1 / f (the mean f); a keypoint takes part if ray_valid and the
+ * rule above; e1_W = C_WC1 normalised(ray). It walks the candidates that are not 3D. For a candidate
+ * with dist < best: if e0 . e1 < cos 6 sigma, with et = normalised(r_WC1 - r0), n0 = normalised(e0 x
+ * et), n1 = normalised(e1 x et), it is rejected if n0 . n1 < cos 6 sigma or (e0 x e1) . normalised(n0 +
+ * n0) > 0 (n0 twice, as written at :1914); then triangulateFast(r0, e0, r_WC1, e1, sigma); rejected if
+ * not valid or if the point is closer than 0.2 m to r0 or to r_WC1. If the landmark is the one the
+ * keypoint carries, n_records grows by 1 and the landmark's remaining slots are left, nothing else
+ * changing; otherwise it is a record (best, match, n_records) and the triangulated point is stored
+ * only if the result is not parallel: `point` is that of the keypoint's last non-parallel record,
+ * which may belong to an earlier landmark than its match, and zero when there is none.
+ * Both passes are independent of the reference's thread count; the result equals the serial walk's:
+ * the match is the first candidate in order attaining the minimum over the admissible ones, the
+ * records are the strict prefix minima.
+ * The reference's per-thread reprErr (:1821, :1826) is the sum of the reprojection distances of a
+ * thread's records over their count; the caller forms it from n_records and record_repr_sum of the
+ * thread's keypoints. That regrouping of the sum changes rounding only.
+ *
+ * Independent of the problem set with okvisgpu_set_problems (needs none, leaves the device parameter
+ * sets alone); uses the context's device and stream and returns with the results in the caller's
+ * arrays. A job's result does not depend on the other jobs of the batch and is the same bits on every
+ * run. n_jobs = 0, jobs without keypoints and maps without landmarks or observations are valid (-1 /
+ * zero outputs). OKVISGPU_ERR_INVALID_ARGUMENT, before anything is launched or written, for a NULL ctx,
+ * batch or result, missing arrays, a CSR array not starting at 0 or not monotone, a camera, pose, pass
+ * or carried-landmark index out of range, and between okvisgpu_solve_begin and _solve_end;
+ * okvisgpu_last_error names the offender. */
+typedef struct okvisgpu_match_batch {
+  /* --- the map */
+  int32_t n_poses;
+  const double* poses;              /* [n_poses][7] T_WS of the old frames                         */
+  int32_t n_cameras;
+  const okvisgpu_camera* cameras;   /* [n_cameras]                                                 */
+  const double* extrinsics;         /* [n_cameras][7] T_SC                                         */
+  int32_t n_landmarks;
+  const double* landmarks;          /* [n_landmarks][4] hp_W, ascending LandmarkId                 */
+  const double* landmark_quality;   /* [n_landmarks]                                               */
+  const uint8_t* landmark_use;      /* [n_landmarks] loopClosureLandmarksToUseExclusively, NULL = all */
+  const int32_t* obs_begin;         /* [n_landmarks+1] CSR: observations of landmark l             */
+  const int32_t* obs_pose;          /* [n_obs] index into poses                                    */
+  const int32_t* obs_camera;        /* [n_obs]                                                     */
+  const uint8_t* obs_descriptor;    /* [n_obs][48]                                                 */
+  const double* obs_ray;            /* [n_obs][3] e_C of getBackProjection, not normalised         */
+  /* --- scalars */
+  int32_t imu_use;                  /* params.imu.use                                              */
+  int32_t loop_closure;             /* 1 = called with a non-null exclusive set                    */
+  double matching_threshold;        /* briskMatchingThreshold_, 60.0 in the reference              */
+  /* --- jobs */
+  int32_t n_jobs;
+  const int32_t* job_camera;        /* [n_jobs]                                                    */
+  const int32_t* job_pass;          /* [n_jobs] 0 / 1                                              */
+  const double* job_pose_prepare;   /* [n_jobs][7] T_WS1 when the candidates were prepared         */
+  const double* job_pose_match;     /* [n_jobs][7] T_WS1 now (pass 1 runs after a solve moved it)  */
+  const int32_t* kp_begin;          /* [n_jobs+1] CSR into the keypoint arrays                     */
+  /* --- keypoints */
+  const double* keypoint;           /* [n_kp][2]                                                   */
+  const uint8_t* descriptor;        /* [n_kp][48]                                                  */
+  const double* ray;                /* [n_kp][3] the back-projection ...                           */
+  const uint8_t* ray_valid;         /* [n_kp]    ... and its bool                                  */
+  const int32_t* landmark;          /* [n_kp] index of the landmark the keypoint carries, -1 = none */
+} okvisgpu_match_batch;
+
+typedef struct okvisgpu_match_result {  /* caller-owned, any may be NULL */
+  int32_t* match_landmark;          /* [n_kp] landmark index, -1 = none                            */
+  int32_t* match_distance;          /* [n_kp] Hamming distance of the match, -1 = none             */
+  int32_t* n_records;               /* [n_kp]                                                      */
+  double* record_repr_sum;          /* [n_kp] pass 0 (0 in a pass-1 job)                           */
+  double* point;                    /* [n_kp][4] pass 1 (0 in a pass-0 job)                        */
+  int32_t* cand_n;                  /* [n_jobs][n_landmarks] -1 = not a candidate, else 1..3 slots */
+  uint8_t* cand_is3d;               /* [n_jobs][n_landmarks]                                       */
+  int32_t* cand_obs;                /* [n_jobs][n_landmarks][3] observation of each slot, -1 unused */
+  double* cand_projection;          /* [n_jobs][n_landmarks][2] (0 for a non-candidate)            */
+} okvisgpu_match_result;
+int okvisgpu_match_to_map(okvisgpu_ctx* ctx, const okvisgpu_match_batch* batch, okvisgpu_match_result* result);
+
 /* ---------------------------------------------------------------- post-solve landmark pass
  * (An addition to ABI 6: a new entry point and a new struct; no existing struct or call changes, so
  * OKVISGPU_ABI_VERSION stays 6 and a caller built against the earlier header keeps working.)

@@ -370,4 +370,47 @@ struct TwoPoseExtrEvalDev {
   double* J_extr;             // [n][n_cam][D][6]
 };
 
+// Frontend::matchToMap for a batch of jobs over one map (okvisgpu_match_batch on device;
+// kernels_match.hip). A camera row is DevProblem::cam's followed by the image width and height.
+constexpr int kMatchCamDoubles = kCamDoubles + 2;
+struct MatchDev {
+  int32_t n_jobs, n_lm, n_kp0, n_kp1;  // keypoints of the pass-0 / pass-1 jobs
+  int32_t imu_use, loop_closure;
+  double threshold;
+  const double* poses;            // [n_poses][7]
+  const double* cam;              // [n_cam][kMatchCamDoubles]
+  const double* extr;             // [n_cam][7]
+  const double* lm;               // [n_lm][4]
+  const double* lm_quality;       // [n_lm]
+  const uint8_t* lm_use;          // [n_lm] or nullptr (all)
+  const int32_t* obs_begin;       // [n_lm+1]
+  const int32_t* obs_pose;        // [n_obs]
+  const int32_t* obs_cam;         // [n_obs]
+  const uint32_t* obs_desc;       // [n_obs][12]
+  const double* obs_ray;          // [n_obs][3]
+  const int32_t* job_cam;         // [n_jobs]
+  const double* job_pose_prepare; // [n_jobs][7]
+  const double* job_pose_match;   // [n_jobs][7]
+  const int32_t* kp_list;         // [n_kp0 + n_kp1] keypoint indices, the pass-0 jobs' first
+  const int32_t* kp_job;          // [n_kp]
+  const double* kp_xy;            // [n_kp][2]
+  const uint32_t* kp_desc;        // [n_kp][12]
+  const double* kp_ray;           // [n_kp][3]
+  const uint8_t* kp_ray_valid;    // [n_kp]
+  const int32_t* kp_lm;           // [n_kp] carried landmark or -1
+  // candidate tables, [n_jobs][n_lm]: the outputs, and per slot what the match kernels read
+  int32_t* cand_n;
+  uint8_t* cand_is3d;
+  int32_t* cand_obs;              // [..][3]
+  double* cand_proj;              // [..][2]
+  double* cand_geo;               // [..][3][6] e0_W | r0_W
+  uint32_t* cand_desc;            // [..][3][12]
+  // per keypoint
+  int32_t* out_match;
+  int32_t* out_dist;
+  int32_t* out_records;
+  double* out_sum;
+  double* out_point;              // [n_kp][4]
+};
+
 }  // namespace okg

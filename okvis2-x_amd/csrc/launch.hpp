@@ -87,6 +87,12 @@ void launch_twopose_compute(const TwoPoseDev& T, hipStream_t s);
 void launch_twopose_extr_compute(const TwoPoseExtrDev& T, hipStream_t s);
 void launch_twopose_extr_eval(const TwoPoseExtrEvalDev& T, hipStream_t s);
 
+// Frontend::matchToMap (kernels_match.hip; okvisgpu_match_to_map): the candidate tables of every
+// (job, landmark), one lane each, then one wavefront per keypoint of the pass-0 and of the pass-1
+// jobs. Every element of the tables and of the per-keypoint outputs is written.
+void launch_match_prepare(const MatchDev& M, hipStream_t s);
+void launch_match(const MatchDev& M, hipStream_t s);
+
 // post-solve landmark pass (kernels_landmarks.hip): ViGraph::updateLandmarks on parameter set 0 (run
 // launch_select_current first), one lane per landmark. Outputs in device order: quality [n_lm],
 // flags [n_lm] (kLmInitialised | kLmReset | kLmNotInFront), obs_err [n_obs]; dirs [n_obs][3] is

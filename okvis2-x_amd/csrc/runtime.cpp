@@ -221,6 +221,10 @@ struct okvisgpu_ctx {
   // covariance | Jacobian): likewise
   void* propScratch = nullptr;
   size_t propScratchBytes = 0;
+  // okvisgpu_match_to_map's device arrays (map | jobs | keypoints || per-slot scratch || candidate
+  // tables | per-keypoint outputs): likewise
+  void* matchScratch = nullptr;
+  size_t matchScratchBytes = 0;
 
   void fillSummaries(const std::vector<WinState>& st, okvisgpu_summary* sums) {
     if (!sums) return;
@@ -281,6 +285,7 @@ struct okvisgpu_ctx {
     if (lmScratch) (void)hipFree(lmScratch);
     if (covisScratch) (void)hipFree(covisScratch);
     if (propScratch) (void)hipFree(propScratch);
+    if (matchScratch) (void)hipFree(matchScratch);
     for (hipEvent_t e : forkEv) (void)hipEventDestroy(e);
     for (hipStream_t q : side)
       if (q) (void)hipStreamDestroy(q);
@@ -1907,6 +1912,179 @@ int okvisgpu_imu_propagate(okvisgpu_ctx* c, const okvisgpu_imu_propagate_batch* 
       if (A->jacobian) std::memcpy(A->jacobian + 225 * i, host + o_jac + 1800 * i, 1800);
     }
     if (steps) std::memcpy(steps, st, 4 * n);
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_match_to_map(okvisgpu_ctx* c, const okvisgpu_match_batch* A, okvisgpu_match_result* R) {
+  if (!c || !A || !R) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_to_map: bad arguments");
+  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_to_map: call after solve_end");
+  if (A->n_jobs < 0 || A->n_landmarks < 0 || A->n_poses < 0 || A->n_cameras < 0)
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_to_map: negative count");
+  if (A->n_jobs == 0) return OKVISGPU_OK;
+  return guarded(c, [&]() {
+    const std::string who = "match_to_map: ";
+    const size_t nj = (size_t)A->n_jobs, nl = (size_t)A->n_landmarks, nc = (size_t)A->n_cameras;
+    if (!A->job_camera || !A->job_pass || !A->job_pose_prepare || !A->job_pose_match || !A->kp_begin)
+      throw ArgError{who + "job arrays missing"};
+    if (!nc || !A->cameras || !A->extrinsics) throw ArgError{who + "cameras missing"};
+    if (A->kp_begin[0] != 0) throw ArgError{who + "kp_begin must start at 0"};
+    for (size_t j = 0; j < nj; ++j)
+      if (A->kp_begin[j + 1] < A->kp_begin[j]) throw ArgError{who + "kp_begin not monotone at job " + std::to_string(j)};
+    const size_t nk = (size_t)A->kp_begin[nj];
+    if (nk && (!A->keypoint || !A->descriptor || !A->ray || !A->ray_valid || !A->landmark))
+      throw ArgError{who + "keypoint arrays missing"};
+    if (nl && (!A->landmarks || !A->landmark_quality || !A->obs_begin)) throw ArgError{who + "landmark arrays missing"};
+    if (nl && A->obs_begin[0] != 0) throw ArgError{who + "obs_begin must start at 0"};
+    for (size_t l = 0; l < nl; ++l)
+      if (A->obs_begin[l + 1] < A->obs_begin[l])
+        throw ArgError{who + "obs_begin not monotone at landmark " + std::to_string(l)};
+    const size_t no = nl ? (size_t)A->obs_begin[nl] : 0;
+    if (no && (!A->obs_pose || !A->obs_camera || !A->obs_descriptor || !A->obs_ray || !A->poses))
+      throw ArgError{who + "observation arrays missing"};
+    for (size_t o = 0; o < no; ++o) {
+      if (A->obs_pose[o] < 0 || A->obs_pose[o] >= A->n_poses)
+        throw ArgError{who + "obs_pose out of range at observation " + std::to_string(o)};
+      if (A->obs_camera[o] < 0 || A->obs_camera[o] >= A->n_cameras)
+        throw ArgError{who + "obs_camera out of range at observation " + std::to_string(o)};
+    }
+    size_t nk0 = 0;
+    for (size_t j = 0; j < nj; ++j) {
+      if (A->job_camera[j] < 0 || A->job_camera[j] >= A->n_cameras)
+        throw ArgError{who + "job_camera out of range at job " + std::to_string(j)};
+      if (A->job_pass[j] != 0 && A->job_pass[j] != 1) throw ArgError{who + "job_pass not 0 / 1 at job " + std::to_string(j)};
+      if (A->job_pass[j] == 0) nk0 += (size_t)(A->kp_begin[j + 1] - A->kp_begin[j]);
+    }
+    for (size_t k = 0; k < nk; ++k)
+      if (A->landmark[k] < -1 || A->landmark[k] >= A->n_landmarks)
+        throw ArgError{who + "carried landmark out of range at keypoint " + std::to_string(k)};
+    std::vector<double> cam((size_t)kMatchCamDoubles * nc);
+    for (size_t k = 0; k < nc; ++k) {
+      const okvisgpu_camera& q = A->cameras[k];
+      if (q.distortion < 0 || q.distortion > 3) throw ArgError{who + "unknown distortion model of camera " + std::to_string(k)};
+      const double cv[kMatchCamDoubles] = {(double)q.distortion, q.fu, q.fv, q.cu, q.cv, q.dist[0], q.dist[1], q.dist[2],
+                                           q.dist[3], q.dist[4], q.dist[5], q.dist[6], q.dist[7], (double)q.width,
+                                           (double)q.height};
+      std::memcpy(&cam[kMatchCamDoubles * k], cv, sizeof(cv));
+    }
+    HIPCHK(hipSetDevice(c->device));
+    // device and pinned staging share one layout: uploaded [0, upEnd), read back [downBegin, downEnd),
+    // then the per-slot scratch only the device holds
+    const size_t njl = nj * nl;
+    Arena M;
+    const size_t o_pose = M.reserve(56 * (size_t)A->n_poses), o_cam = M.reserve(8 * cam.size()), o_ext = M.reserve(56 * nc),
+                 o_lm = M.reserve(32 * nl), o_q = M.reserve(8 * nl), o_use = M.reserve(nl), o_ob = M.reserve(4 * (nl + 1)),
+                 o_op = M.reserve(4 * no), o_oc = M.reserve(4 * no), o_od = M.reserve(48 * no), o_or = M.reserve(24 * no),
+                 o_jc = M.reserve(4 * nj), o_jp = M.reserve(56 * nj), o_jm = M.reserve(56 * nj), o_kl = M.reserve(4 * nk),
+                 o_kj = M.reserve(4 * nk), o_kxy = M.reserve(16 * nk), o_kd = M.reserve(48 * nk), o_kr = M.reserve(24 * nk),
+                 o_kv = M.reserve(nk), o_klm = M.reserve(4 * nk);
+    const size_t upEnd = M.size;
+    const size_t o_cn = M.reserve(4 * njl), downBegin = o_cn, o_c3 = M.reserve(njl), o_co = M.reserve(12 * njl),
+                 o_cp = M.reserve(16 * njl), o_m = M.reserve(4 * nk), o_d = M.reserve(4 * nk), o_r = M.reserve(4 * nk),
+                 o_s = M.reserve(8 * nk), o_pt = M.reserve(32 * nk);
+    const size_t downEnd = M.size;
+    const size_t o_geo = M.reserve(144 * njl), o_desc = M.reserve(144 * njl);
+    if (M.size > c->matchScratchBytes) {
+      if (c->matchScratch) HIPCHK(hipFree(c->matchScratch));
+      c->matchScratch = nullptr;
+      c->matchScratchBytes = 0;
+      HIPCHK(hipMalloc(&c->matchScratch, M.size));
+      c->matchScratchBytes = M.size;
+    }
+    char* dev = static_cast<char*>(c->matchScratch);
+    char* host = c->paramStage(downEnd);
+    auto put = [&](size_t off, const void* src, size_t bytes) {
+      if (bytes) std::memcpy(host + off, src, bytes);
+    };
+    put(o_pose, A->poses, 56 * (size_t)A->n_poses);
+    put(o_cam, cam.data(), 8 * cam.size());
+    put(o_ext, A->extrinsics, 56 * nc);
+    put(o_lm, A->landmarks, 32 * nl);
+    put(o_q, A->landmark_quality, 8 * nl);
+    if (A->landmark_use) put(o_use, A->landmark_use, nl);
+    if (nl) put(o_ob, A->obs_begin, 4 * (nl + 1));
+    put(o_op, A->obs_pose, 4 * no);
+    put(o_oc, A->obs_camera, 4 * no);
+    put(o_od, A->obs_descriptor, 48 * no);
+    put(o_or, A->obs_ray, 24 * no);
+    put(o_jc, A->job_camera, 4 * nj);
+    put(o_jp, A->job_pose_prepare, 56 * nj);
+    put(o_jm, A->job_pose_match, 56 * nj);
+    {  // the keypoints of the pass-0 jobs, then those of the pass-1 jobs; the job of every keypoint
+      int32_t* list = reinterpret_cast<int32_t*>(host + o_kl);
+      int32_t* job = reinterpret_cast<int32_t*>(host + o_kj);
+      size_t at0 = 0, at1 = nk0;
+      for (size_t j = 0; j < nj; ++j)
+        for (int32_t k = A->kp_begin[j]; k < A->kp_begin[j + 1]; ++k) {
+          job[k] = (int32_t)j;
+          list[A->job_pass[j] == 0 ? at0++ : at1++] = k;
+        }
+    }
+    put(o_kxy, A->keypoint, 16 * nk);
+    put(o_kd, A->descriptor, 48 * nk);
+    put(o_kr, A->ray, 24 * nk);
+    put(o_kv, A->ray_valid, nk);
+    put(o_klm, A->landmark, 4 * nk);
+    HIPCHK(hipMemcpyAsync(dev, host, upEnd, hipMemcpyHostToDevice, c->stream));
+    MatchDev D{};
+    D.n_jobs = A->n_jobs;
+    D.n_lm = A->n_landmarks;
+    D.n_kp0 = (int32_t)nk0;
+    D.n_kp1 = (int32_t)(nk - nk0);
+    D.imu_use = A->imu_use ? 1 : 0;
+    D.loop_closure = A->loop_closure ? 1 : 0;
+    D.threshold = A->matching_threshold;
+    auto at = [&](size_t off) { return dev + off; };
+    D.poses = reinterpret_cast<const double*>(at(o_pose));
+    D.cam = reinterpret_cast<const double*>(at(o_cam));
+    D.extr = reinterpret_cast<const double*>(at(o_ext));
+    D.lm = reinterpret_cast<const double*>(at(o_lm));
+    D.lm_quality = reinterpret_cast<const double*>(at(o_q));
+    D.lm_use = A->landmark_use ? reinterpret_cast<const uint8_t*>(at(o_use)) : nullptr;
+    D.obs_begin = reinterpret_cast<const int32_t*>(at(o_ob));
+    D.obs_pose = reinterpret_cast<const int32_t*>(at(o_op));
+    D.obs_cam = reinterpret_cast<const int32_t*>(at(o_oc));
+    D.obs_desc = reinterpret_cast<const uint32_t*>(at(o_od));
+    D.obs_ray = reinterpret_cast<const double*>(at(o_or));
+    D.job_cam = reinterpret_cast<const int32_t*>(at(o_jc));
+    D.job_pose_prepare = reinterpret_cast<const double*>(at(o_jp));
+    D.job_pose_match = reinterpret_cast<const double*>(at(o_jm));
+    D.kp_list = reinterpret_cast<const int32_t*>(at(o_kl));
+    D.kp_job = reinterpret_cast<const int32_t*>(at(o_kj));
+    D.kp_xy = reinterpret_cast<const double*>(at(o_kxy));
+    D.kp_desc = reinterpret_cast<const uint32_t*>(at(o_kd));
+    D.kp_ray = reinterpret_cast<const double*>(at(o_kr));
+    D.kp_ray_valid = reinterpret_cast<const uint8_t*>(at(o_kv));
+    D.kp_lm = reinterpret_cast<const int32_t*>(at(o_klm));
+    D.cand_n = reinterpret_cast<int32_t*>(at(o_cn));
+    D.cand_is3d = reinterpret_cast<uint8_t*>(at(o_c3));
+    D.cand_obs = reinterpret_cast<int32_t*>(at(o_co));
+    D.cand_proj = reinterpret_cast<double*>(at(o_cp));
+    D.cand_geo = reinterpret_cast<double*>(at(o_geo));
+    D.cand_desc = reinterpret_cast<uint32_t*>(at(o_desc));
+    D.out_match = reinterpret_cast<int32_t*>(at(o_m));
+    D.out_dist = reinterpret_cast<int32_t*>(at(o_d));
+    D.out_records = reinterpret_cast<int32_t*>(at(o_r));
+    D.out_sum = reinterpret_cast<double*>(at(o_s));
+    D.out_point = reinterpret_cast<double*>(at(o_pt));
+    launch_match_prepare(D, c->stream);
+    HIPCHK(hipGetLastError());
+    launch_match(D, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host + downBegin, dev + downBegin, downEnd - downBegin, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    auto get = [&](void* dst, size_t off, size_t bytes) {
+      if (dst && bytes) std::memcpy(dst, host + off, bytes);
+    };
+    get(R->cand_n, o_cn, 4 * njl);
+    get(R->cand_is3d, o_c3, njl);
+    get(R->cand_obs, o_co, 12 * njl);
+    get(R->cand_projection, o_cp, 16 * njl);
+    get(R->match_landmark, o_m, 4 * nk);
+    get(R->match_distance, o_d, 4 * nk);
+    get(R->n_records, o_r, 4 * nk);
+    get(R->record_repr_sum, o_s, 8 * nk);
+    get(R->point, o_pt, 32 * nk);
     return (int)OKVISGPU_OK;
   });
 }

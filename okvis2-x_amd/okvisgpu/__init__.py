@@ -195,6 +195,23 @@ class ImuPropagateBatch(C.Structure):
                 ("sample_gyr_acc", _dp), ("covariance", _dp), ("jacobian", _dp)]
 
 
+class MatchBatch(C.Structure):
+    """okvisgpu_match_batch: one map and the jobs (camera image x pass) matched against it."""
+    _fields_ = [("n_poses", C.c_int32), ("poses", _dp), ("n_cameras", C.c_int32), ("cameras", C.POINTER(Camera)),
+                ("extrinsics", _dp), ("n_landmarks", C.c_int32), ("landmarks", _dp), ("landmark_quality", _dp),
+                ("landmark_use", _up), ("obs_begin", _ip), ("obs_pose", _ip), ("obs_camera", _ip),
+                ("obs_descriptor", _up), ("obs_ray", _dp), ("imu_use", C.c_int32), ("loop_closure", C.c_int32),
+                ("matching_threshold", C.c_double), ("n_jobs", C.c_int32), ("job_camera", _ip), ("job_pass", _ip),
+                ("job_pose_prepare", _dp), ("job_pose_match", _dp), ("kp_begin", _ip), ("keypoint", _dp),
+                ("descriptor", _up), ("ray", _dp), ("ray_valid", _up), ("landmark", _ip)]
+
+
+class MatchResult(C.Structure):
+    """okvisgpu_match_result: the caller-owned outputs of okvisgpu_match_to_map (any may be NULL)."""
+    _fields_ = [("match_landmark", _ip), ("match_distance", _ip), ("n_records", _ip), ("record_repr_sum", _dp),
+                ("point", _dp), ("cand_n", _ip), ("cand_is3d", _up), ("cand_obs", _ip), ("cand_projection", _dp)]
+
+
 class TwoPoseEdges(C.Structure):
     _fields_ = [("n_edges", C.c_int32), ("ref_pose", _dp), ("other_pose", _dp),
                 ("n_cameras", C.c_int32), ("cameras", C.POINTER(Camera)), ("extrinsics", _dp),
@@ -238,6 +255,7 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_eval_host", "okvisgpu_plan_window", "okvisgpu_loss_evaluate", "okvisgpu_plan_digest",
     "okvisgpu_launch_regime", "okvisgpu_update_landmarks", "okvisgpu_covisibilities", "okvisgpu_imu_propagate",
     "okvisgpu_twopose_extrinsics_compute", "okvisgpu_twopose_extrinsics_evaluate", "okvisgpu_gauss_newton_step",
+    "okvisgpu_match_to_map",
 ]
 N_PHASES = 15
 TWOPOSE_MAX_CAMERAS = 6
@@ -304,6 +322,7 @@ def lib():
         L.okvisgpu_launch_regime.argtypes = [C.c_int32] * 9 + [_ip]
         L.okvisgpu_imu_append.argtypes = [C.c_void_p, C.POINTER(ImuAppendBatch), _ip]
         L.okvisgpu_imu_propagate.argtypes = [C.c_void_p, C.POINTER(ImuPropagateBatch), _ip]
+        L.okvisgpu_match_to_map.argtypes = [C.c_void_p, C.POINTER(MatchBatch), C.POINTER(MatchResult)]
         L.okvisgpu_twopose_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _dp, _dp]
         L.okvisgpu_twopose_extrinsics_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _up, _dp,
                                                           _dp]
@@ -539,6 +558,37 @@ def imu_propagate_batch(imu_params, poses, speed_biases, t_start, t_end, sample_
     if jacobian is not None:
         b.jacobian = dptr(jacobian)
     return b, keep + [poses, speed_biases, covariance, jacobian]
+
+
+def match_batch(poses, cameras, extrinsics, landmarks, landmark_quality, obs_begin, obs_pose, obs_camera,
+                obs_descriptor, obs_ray, job_camera, job_pass, job_pose_prepare, job_pose_match, kp_begin, keypoint,
+                descriptor, ray, ray_valid, landmark, landmark_use=None, imu_use=True, loop_closure=False,
+                matching_threshold=60.0):
+    """An okvisgpu_match_batch over numpy arrays (copied to the struct's types where they differ):
+    (struct, arrays it points into). `cameras` is a sequence of Camera; the other arguments are the
+    arrays of the header's struct, `landmark_use` None = NULL (all landmarks)."""
+    f8 = lambda a, *shape: np.ascontiguousarray(a, dtype=np.float64).reshape(*shape)
+    i4 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    u1 = lambda a, *shape: np.ascontiguousarray(a, dtype=np.uint8).reshape(*shape)
+    cams = (Camera * max(1, len(cameras)))(*cameras)
+    k = {"poses": f8(poses, -1, 7), "extrinsics": f8(extrinsics, -1, 7), "landmarks": f8(landmarks, -1, 4),
+         "landmark_quality": f8(landmark_quality, -1), "obs_begin": i4(obs_begin), "obs_pose": i4(obs_pose),
+         "obs_camera": i4(obs_camera), "obs_descriptor": u1(obs_descriptor, -1, 48), "obs_ray": f8(obs_ray, -1, 3),
+         "job_camera": i4(job_camera), "job_pass": i4(job_pass), "job_pose_prepare": f8(job_pose_prepare, -1, 7),
+         "job_pose_match": f8(job_pose_match, -1, 7), "kp_begin": i4(kp_begin), "keypoint": f8(keypoint, -1, 2),
+         "descriptor": u1(descriptor, -1, 48), "ray": f8(ray, -1, 3), "ray_valid": u1(ray_valid, -1),
+         "landmark": i4(landmark)}
+    if landmark_use is not None:
+        k["landmark_use"] = u1(landmark_use, -1)
+    b = MatchBatch()
+    b.n_poses, b.n_cameras, b.n_landmarks = len(k["poses"]), len(cameras), len(k["landmarks"])
+    b.n_jobs = len(k["job_camera"])
+    b.cameras = cams
+    b.imu_use, b.loop_closure, b.matching_threshold = int(bool(imu_use)), int(bool(loop_closure)), matching_threshold
+    for name, a in k.items():
+        ptr = {np.dtype(np.float64): _dp, np.dtype(np.int32): _ip, np.dtype(np.uint8): _up}[a.dtype]
+        setattr(b, name, a.ctypes.data_as(ptr))
+    return b, (cams, k)
 
 
 class TwoPoseBatch:
@@ -813,6 +863,26 @@ class Context:
                     "okvisgpu_imu_propagate")
         out = (steps,) + ((P,) if P is not None else ()) + ((J,) if J is not None else ())
         return out[0] if len(out) == 1 else out
+
+    def match_to_map(self, batch: MatchBatch, fill=None):
+        """okvisgpu_match_to_map (Frontend::matchToMap's candidate preparation and both matching passes)
+        for a batch built by match_batch(): dict of match_landmark, match_distance, n_records
+        [n_kp], record_repr_sum [n_kp], point [n_kp, 4], cand_n, cand_is3d [n_jobs, n_landmarks], cand_obs
+        [.., 3], cand_projection [.., 2]. `fill` (a dict of per-output values) pre-fills the arrays
+        the call writes into."""
+        nj, nl = batch.n_jobs, batch.n_landmarks
+        nk = int(batch.kp_begin[nj]) if batch.kp_begin else 0
+        spec = {"match_landmark": ((nk,), np.int32), "match_distance": ((nk,), np.int32), "n_records": ((nk,), np.int32),
+                "record_repr_sum": ((nk,), np.float64), "point": ((nk, 4), np.float64), "cand_n": ((nj, nl), np.int32),
+                "cand_is3d": ((nj, nl), np.uint8), "cand_obs": ((nj, nl, 3), np.int32),
+                "cand_projection": ((nj, nl, 2), np.float64)}
+        out = {k: np.full(shape, (fill or {}).get(k, 0), dtype=dt) for k, (shape, dt) in spec.items()}
+        r = MatchResult()
+        for k, a in out.items():
+            setattr(r, k, a.ctypes.data_as({np.dtype(np.float64): _dp, np.dtype(np.int32): _ip,
+                                            np.dtype(np.uint8): _up}[a.dtype]))
+        self._check(lib().okvisgpu_match_to_map(self.h, C.byref(batch), C.byref(r)), "okvisgpu_match_to_map")
+        return out
 
     def twopose_compute(self, edges: "TwoPoseBatch"):
         """TwoPoseStandardGraphError::compute for every edge of the batch: dict of DeltaX_ [n,6],
