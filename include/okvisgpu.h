@@ -759,6 +759,23 @@ int okvisgpu_plan_digest(const okvisgpu_problem* problems, int32_t n_windows, in
                          int32_t capacity, int32_t* n_entries, char* names, int32_t* region, int64_t* bytes,
                          uint64_t* hash);
 
+/* Host-only: the assembly work items of a batch's plan as the records the assembly kernels read,
+ * beside what the planner's separate arrays hold for the same items (no device, no context;
+ * development, tests/test_assembly_paths.py). Items in kernel order: the heavy pose-pose list, the
+ * light pose-pose list, the speed/bias list (pads of the XCD interleave included).
+ *   counts[4]:      items of the three lists, records in all
+ *   records[12 i]:  window (-1: pad, the rest 0), visit run begin, partial-block run begin, factor run
+ *                   begin, end, f-vector index of the row block, of the column block, leading
+ *                   dimension of S, S element offset (low, high word), flags (1 diagonal, 2 / 4 the
+ *                   row / column block is a speed/bias block), 0
+ *   arrays[16 i]:   pair (-1: pad, the rest 0), pair_win, pair_cbegin[pair], pair_runs[pair][0..1],
+ *                   pair_cbegin[pair + 1], pair_fi, pair_fj, fb_off[fi], fb_off[fj], fb_kind[fi],
+ *                   fb_kind[fj], win_foff, win_fpad, win_soff, 0
+ * for i < min(capacity, counts[3]); records / arrays may be NULL. Size them from a first call with
+ * capacity 0. */
+int okvisgpu_plan_assembly(const okvisgpu_problem* problems, int32_t n_windows, int32_t cu_count, int32_t* counts,
+                           int32_t capacity, int32_t* records, int64_t* arrays);
+
 /* Host-only: what the batch size decides about the launches of a solve on a device of cu_count
  * compute units (no device, no context; development, tests/test_launch_regime.py). any_split: a
  * window has a nested-dissection split; persistent_fits / pipe_fits: the persistent / pipelined

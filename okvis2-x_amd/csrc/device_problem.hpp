@@ -58,6 +58,22 @@ struct Contrib {
 };
 
 
+// One assembly work item (a block pair) as the assembly kernels read it: everything the pair's walk
+// needs from pair_win / pair_cbegin / pair_runs / pair_fi / pair_fj / fb_off / fb_kind / win_foff /
+// win_fpad / win_soff in one 48-byte record (three 16-byte loads), in item order (the XCD-grouped
+// lists of asm_*_items, pads included: win = -1).
+struct AsmRec {
+  int32_t win;             // window (-1: pad item, every other field 0)
+  int32_t cb, pb, ob, ce;  // contribution runs: visits [cb, pb), partial blocks [pb, ob), factors [ob, ce)
+  int32_t fi, fj;          // index of the row / column block's first entry in the f-vectors (win_foff + fb_off)
+  int32_t ld;              // leading dimension of the window's S (win_fpad)
+  int64_t dst;             // element offset of the block's first entry in S
+  int32_t flags;           // bit 0 diagonal pair, bit 1 / 2 the row / column block is a speed/bias block
+  int32_t pad_;
+};
+static_assert(sizeof(AsmRec) == 48, "three 16-byte loads");
+constexpr int kAsmRecInts = sizeof(AsmRec) / 4;
+
 struct WinState {
   double radius, mu;
   double x_cost, cand_cost, fixed_cost, initial_cost, min_cost;
@@ -259,6 +275,7 @@ struct DevProblem {
   int32_t n_asm_pp, n_asm_sb;
   const int32_t* asm_ppl_items;     // light pose-pose pairs (off-diagonal, few contributions): 16 lanes each
   int32_t n_asm_ppl;
+  int32_t n_tiles;
   const int32_t* pair_win;         // [n_pair]
   const int32_t* pair_fi;          // global f-block index (row, fi >= fj)
   const int32_t* pair_fj;
@@ -291,7 +308,9 @@ struct DevProblem {
   const int16_t* tile_fu;            // per window T x T (same offsets): the first step whose band update
                                      // writes tile (i, j) (kNoUpdate if none): before it the tile is read from S
   const int64_t* win_tnzoff;         // [n_win] offset of the window's flags in tile_nz
-  int32_t n_tiles;
+  // the items of asm_pp_items, then asm_ppl_items, then asm_sb_items as records (HostBatch::asm_rec);
+  // a context-owned buffer outside the arena table (runtime.cpp), set after the arena is patched
+  const AsmRec* asm_rec;             // [n_asm_pp + n_asm_ppl + n_asm_sb]
   double* chol_defer;              // split persistent schedule: the right part's rhs contributions
   const int64_t* win_defoff;       //   to the separator's rows, [T - tS][tS - tL][64] per window
   double* fwdF;                    // per window fpad: forward-substitution work vector
@@ -310,6 +329,10 @@ struct DevProblem {
   WinState* st;                    // [n_win]
   DevOptions opt;
 };
+
+// (the arena table reserves sizeof(DevProblem) for `self`, and tests/golden/plan_digest.json pins that
+// entry's byte count: a new member goes where the alignment leaves room)
+static_assert(sizeof(DevProblem) == 1664, "the plan digest pins the size of the descriptor");
 
 // Batch of TwoPoseStandardGraphError::compute inputs (okvisgpu_twopose_edges on device) and the
 // per-edge output record: DeltaX_ [6] | J_ [36] | linearisation point [7] | H00_ [36] | b0_ [6].

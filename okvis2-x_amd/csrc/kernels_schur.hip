@@ -870,30 +870,51 @@ __global__ __launch_bounds__(256) void k_zero_S(const DevProblem* __restrict__ P
 // its own Y row, and two steps of descriptors/operands are in flight per lane.
 constexpr int kGroups = 8;
 
+// The work item's record (AsmRec, device_problem.hpp): three 16-byte loads, the only load level
+// between the item number and the window state, the first descriptors and the scales.
+__device__ __forceinline__ AsmRec loadAsmRec(const DevProblem& P, int idx) {
+  const auto q = reinterpret_cast<gptr<int4>>(gmem(P.asm_rec) + idx);
+  const int4 a = q[0], b = q[1], c = q[2];
+  AsmRec R;
+  R.win = a.x; R.cb = a.y; R.pb = a.z; R.ob = a.w;
+  R.ce = b.x; R.fi = b.y; R.fj = b.z; R.ld = b.w;
+  R.dst = (int64_t)(((uint64_t)(uint32_t)c.y << 32) | (uint32_t)c.x);
+  R.flags = c.z; R.pad_ = 0;
+  return R;
+}
+// The closing expression of a pose-pose entry, one function for both kernels (the compiler
+// contracts it the same way in each): s_i s_j H - Sc, plus the damping d^2 on the diagonal.
+__device__ __forceinline__ double asmClosePP(double si, double sj, double H, double Sc) { return si * sj * H - Sc; }
+__device__ __forceinline__ double asmDamped(double val, double d) {
+  val += d * d;
+  return val;
+}
+
 __device__ __forceinline__ void asmPairsHeavy(const DevProblem& P, int bid) {
   const int lane = threadIdx.x & 63;
-  const int item = bid * 4 + (threadIdx.x >> 6);
+  const int item = __builtin_amdgcn_readfirstlane(bid * 4 + (int)(threadIdx.x >> 6));  // (wave-uniform: scalar loads)
   if (item >= P.n_asm_pp) return;
-  const int k = __builtin_amdgcn_readfirstlane(gmem(P.asm_pp_items)[item]);  // (wave-uniform: scalar loads)
-  if (k < 0) return;
-  // the pair record in one round of loads; then the window state, the first round of descriptors
-  // and the block offsets in the next, all consumed (empty asm) before the window test, so no load
-  // is sunk behind it
-  const int w = gmem(P.pair_win)[k];
-  const int cb = gmem(P.pair_cbegin)[k], ce = gmem(P.pair_cbegin)[k + 1];
-  const int2 runs = gmem(reinterpret_cast<const int2*>(P.pair_runs))[k];
-  const int pb = runs.x, ob = runs.y;
-  const int fi = gmem(P.pair_fi)[k], fj = gmem(P.pair_fj)[k];
+  const AsmRec R = loadAsmRec(P, item);
+  const int w = R.win;
+  if (w < 0) return;
+  // the record is one round of loads; the window state, the first round of descriptors and the
+  // lane's scales, diagonal and gradient entries are the next, all consumed (empty asm) before
+  // the window test, so no load is sunk behind it
+  const int cb = R.cb, pb = R.pb, ob = R.ob, ce = R.ce;
   const auto pc = gmem(P.pair_contrib);
   const auto gst = gmem(P.st + w);
   const int sDone = gst->done, sNeed = gst->need_gn, sFail = gst->gn_failed, lb = gst->lcur;
   const double sMu = gst->mu;
   const int myc0 = min(cb + lane, max(pb - 1, cb));
   const int da0 = pc[myc0].a, db0 = pc[myc0].b;
-  const int foff = gmem(P.win_foff)[w], offi = gmem(P.fb_off)[fi], offj = gmem(P.fb_off)[fj];
-  asm volatile("" ::"v"(da0), "v"(db0), "v"(foff), "v"(offi), "v"(offj), "v"(cb), "v"(ce), "v"(lb), "v"(sMu));
-  if ((sDone != 0) | (sNeed == 0) | (sFail != 0)) return;
   const int g = lane / 6, r = lane - 6 * (lane / 6);
+  const bool diag = (R.flags & 1) != 0;
+  // one entry per lane (two registers through the walks): group 0 the row scales s_i, group 1 the
+  // column scales s_j, group 2 the diagonal of H, groups 3 and up the gradient; handed to the row lanes at the end
+  const double* fsel = g == 0 ? P.sF + R.fi : g == 1 ? P.sF + R.fj : g == 2 ? P.hdF + R.fi : P.gF + R.fi;
+  const double fent = gmem(fsel)[r];
+  asm volatile("" ::"v"(da0), "v"(db0), "v"(fent), "v"(lb), "v"(sMu));
+  if ((sDone != 0) | (sNeed == 0) | (sFail != 0)) return;
   const bool inGroup = g < kGroups;
   const auto vhg = gmem(P.seg_hg);
   const auto suz = gmem(P.seg_uz);
@@ -985,27 +1006,26 @@ __device__ __forceinline__ void asmPairsHeavy(const DevProblem& P, int bid) {
     }
     uz += __shfl(uz, src, 64);
   }
+  double sj[6];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) sj[q] = __shfl(fent, 6 + q, 64);
+  const double si = fent, hdr = __shfl(fent, min(lane + 12, 63), 64), gfr = __shfl(fent, min(lane + 18, 63), 64);
   if (lane >= 6) return;
-  const bool diag = fi == fj;
-  const double si = gmem(P.sF)[(size_t)foff + offi + r];
-  const auto Srow = gmemw(P.S + gmem(P.win_soff)[w] + (int64_t)(offi + r) * gmem(P.win_fpad)[w] + offj);
+  const auto Srow = gmemw(P.S + R.dst + (int64_t)r * R.ld);
 #pragma unroll
   for (int q = 0; q < 6; ++q) {
-    const double sj = gmem(P.sF)[(size_t)foff + offj + q];
-    double val = si * sj * H[q] - Sc[q];
+    double val = asmClosePP(si, sj[q], H[q], Sc[q]);
     if (diag && r == q) {
-      const size_t idx = (size_t)foff + offi + r;
-      const double dg = sqrt(fmin(fmax(si * si * gmem(P.hdF)[idx], P.opt.min_lm_diagonal), P.opt.max_lm_diagonal));
+      const size_t idx = (size_t)R.fi + r;
+      const double dg = sqrt(fmin(fmax(si * si * hdr, P.opt.min_lm_diagonal), P.opt.max_lm_diagonal));
       gmemw(P.diagF)[idx] = dg;
-      const double d = dg * sqrt(sMu);
-      val += d * d;
+      val = asmDamped(val, dg * sqrt(sMu));
     }
     Srow[q] = val;
   }
   if (diag) {
     // Schur rhs: s_i g_i - sum_visits U_v z_l
-    const size_t idx = (size_t)foff + offi + r;
-    gmemw(P.rhsF)[idx] = gmem(P.sF)[idx] * gmem(P.gF)[idx] - uz;
+    gmemw(P.rhsF)[(size_t)R.fi + r] = si * gfr - uz;
   }
 }
 __global__ __launch_bounds__(256, 6) void k_assemble_pp(const DevProblem* __restrict__ Pp) { asmPairsHeavy(*Pp, (int)blockIdx.x); }
@@ -1018,15 +1038,12 @@ constexpr int kPplLanes = 16, kPplGroups = 2;
 __device__ __forceinline__ void asmPairsLight(const DevProblem& P, int bid) {
   const int lane = threadIdx.x & 63, sub = threadIdx.x & (kPplLanes - 1);
   const int item = (bid * 256 + threadIdx.x) / kPplLanes;
-  const int kRaw = item < P.n_asm_ppl ? gmem(P.asm_ppl_items)[item] : -1;
-  const bool has = kRaw >= 0;
-  const int k = has ? kRaw : 0;
-  // the pair record, then the window state and offsets, consumed before any test (no loads sunk)
-  const int w = gmem(P.pair_win)[k];
-  const int ce = gmem(P.pair_cbegin)[k + 1];
-  const int2 runs = gmem(reinterpret_cast<const int2*>(P.pair_runs))[k];
-  const int pb = runs.x, ob = runs.y;
-  const int fi = gmem(P.pair_fi)[k], fj = gmem(P.pair_fj)[k];
+  // the pair's record (a pad or an item past the list: window -1, read as window 0 and masked), then
+  // the window state, the first descriptors and the scales, consumed before any test (no loads sunk)
+  const AsmRec R = loadAsmRec(P, P.n_asm_pp + min(item, P.n_asm_ppl - 1));
+  const bool has = item < P.n_asm_ppl && R.win >= 0;
+  const int w = max(R.win, 0);
+  const int pb = R.pb, ob = R.ob, ce = R.ce;
   const auto pc = gmem(P.pair_contrib);
   const auto gst = gmem(P.st + w);
   const int sDone = gst->done, sNeed = gst->need_gn, sFail = gst->gn_failed, lb = gst->lcur;
@@ -1038,8 +1055,9 @@ __device__ __forceinline__ void asmPairsLight(const DevProblem& P, int bid) {
   int ai0[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) ai0[u] = pc[max(min(pb + g + u * kPplGroups, ob - 1), 0)].a;
-  const int foff = gmem(P.win_foff)[w], offi = gmem(P.fb_off)[fi], offj = gmem(P.fb_off)[fj];
-  asm volatile("" ::"v"(C0.type), "v"(C0.a), "v"(C0.b), "v"(C0.c), "v"(foff), "v"(offi), "v"(offj), "v"(lb),
+  // (group 0 holds the row scales s_i, the other lanes the column scales s_j: one entry per lane)
+  const double fent = gmem(P.sF)[(size_t)(g == 0 ? R.fi : R.fj) + r];
+  asm volatile("" ::"v"(C0.type), "v"(C0.a), "v"(C0.b), "v"(C0.c), "v"(fent), "v"(lb),
                "v"(ai0[0]), "v"(ai0[1]), "v"(ai0[2]), "v"(ai0[3]));
   const bool live = has & (sDone == 0) & (sNeed != 0) & (sFail == 0);  // gnSelect
   if (!__any(live)) return;
@@ -1104,11 +1122,14 @@ __device__ __forceinline__ void asmPairsLight(const DevProblem& P, int bid) {
     H[q] += __shfl(H[q], src, 64);
     Sc[q] += __shfl(Sc[q], src, 64);
   }
-  if (sub >= 6 || !live) return;
-  const double si = gmem(P.sF)[(size_t)foff + offi + r];
-  const auto Srow = gmemw(P.S + gmem(P.win_soff)[w] + (int64_t)(offi + r) * gmem(P.win_fpad)[w] + offj);
+  double sj[6];
 #pragma unroll
-  for (int q = 0; q < 6; ++q) Srow[q] = si * gmem(P.sF)[(size_t)foff + offj + q] * H[q] - Sc[q];
+  for (int q = 0; q < 6; ++q) sj[q] = __shfl(fent, (lane & ~(kPplLanes - 1)) + 6 + q, 64);
+  const double si = fent;
+  if (sub >= 6 || !live) return;
+  const auto Srow = gmemw(P.S + R.dst + (int64_t)r * R.ld);
+#pragma unroll
+  for (int q = 0; q < 6; ++q) Srow[q] = asmClosePP(si, sj[q], H[q], Sc[q]);
 }
 __global__ __launch_bounds__(256) void k_assemble_pp_light(const DevProblem* __restrict__ Pp) { asmPairsLight(*Pp, (int)blockIdx.x); }
 
@@ -1132,36 +1153,37 @@ __device__ __forceinline__ double sbPriorTerm(const DevProblem& P, const Contrib
 }
 __device__ __forceinline__ void asmPairsSb(const DevProblem& P, int bid) {
   const int lane = threadIdx.x & 63;
-  const int item = bid * 4 + (threadIdx.x >> 6);
-  if (item >= P.n_asm_sb) return;
   // (wave-uniform from here: the pair record and its descriptors go to scalar registers)
-  const int k = __builtin_amdgcn_readfirstlane(gmem(P.asm_sb_items)[item]);
-  // the pair record, then the window state, the block offsets and the first contribution
-  // descriptors, consumed (empty asm) before the window test so that no load is sunk behind it
-  const int w = gmem(P.pair_win)[k], fi = gmem(P.pair_fi)[k], fj = gmem(P.pair_fj)[k];
-  const int cb = gmem(P.pair_cbegin)[k], ce = gmem(P.pair_cbegin)[k + 1];
+  const int item = __builtin_amdgcn_readfirstlane(bid * 4 + (int)(threadIdx.x >> 6));
+  if (item >= P.n_asm_sb) return;
+  // the pair's record, then the window state, the first contribution descriptors and the lane's
+  // first scales, diagonal and gradient entries, consumed (empty asm) before the window test so that
+  // no load is sunk behind it
+  const AsmRec R = loadAsmRec(P, P.n_asm_pp + P.n_asm_ppl + item);
+  const int w = R.win, cb = R.cb, ce = R.ce, ld = R.ld;
   const auto gst = gmem(P.st + w);
   const int sDone = gst->done, sNeed = gst->need_gn, sFail = gst->gn_failed, lb = gst->lcur;
   const double sMu = gst->mu;
-  const int ki = gmem(P.fb_kind)[fi], kj = gmem(P.fb_kind)[fj];
-  const int offi = gmem(P.fb_off)[fi], offj = gmem(P.fb_off)[fj];
-  const int foff = gmem(P.win_foff)[w], ld = gmem(P.win_fpad)[w];
-  const int64_t soff = gmem(P.win_soff)[w];
   const int nc = ce - cb;
   Contrib Cs[kSbPre];
 #pragma unroll
   for (int u = 0; u < kSbPre; ++u) Cs[u] = gmem(P.pair_contrib)[cb + min(u, max(nc - 1, 0))];
-  asm volatile("" ::"v"(ki), "v"(kj), "v"(offi), "v"(offj), "v"(foff), "v"(ld), "v"(soff), "v"(cb), "v"(ce),
-               "v"(lb), "v"(sMu), "v"(Cs[0].a), "v"(Cs[kSbPre - 1].a));
+  const int ni = (R.flags & 2) == 0 ? 6 : 9, nj = (R.flags & 4) == 0 ? 6 : 9;
+  const bool diag = (R.flags & 1) != 0;
+  const int e0 = min(lane, ni * nj - 1), r0 = e0 / nj, q0 = e0 - r0 * nj, l0 = min(lane, ni - 1);
+  const double si0 = gmem(P.sF)[(size_t)R.fi + r0], sj0 = gmem(P.sF)[(size_t)R.fj + q0];
+  const double hd0 = gmem(P.hdF)[(size_t)R.fi + r0];
+  const double sl0 = gmem(P.sF)[(size_t)R.fi + l0], gl0 = gmem(P.gF)[(size_t)R.fi + l0];
+  asm volatile("" ::"v"(si0), "v"(sj0), "v"(hd0), "v"(sl0), "v"(gl0), "v"(lb), "v"(sMu), "v"(Cs[0].a),
+               "v"(Cs[kSbPre - 1].a));
   if ((sDone != 0) | (sNeed == 0) | (sFail != 0)) return;  // gnSelect
-  const int ni = ki == 0 ? 6 : 9, nj = kj == 0 ? 6 : 9;
-  const bool diag = fi == fj;
-  const auto S = gmemw(P.S + soff);
+  const auto S = gmemw(P.S + R.dst);
   const double smu = sqrt(sMu);
   const auto imuH = gmem(P.imu_H);
   for (int e = lane; e < ni * nj; e += 64) {
     const int r = e / nj, q = e - r * nj;
-    const double si = gmem(P.sF)[(size_t)foff + offi + r], sj = gmem(P.sF)[(size_t)foff + offj + q];
+    const bool first = e == lane;  // (the entries loaded with the window state)
+    const double si = first ? si0 : gmem(P.sF)[(size_t)R.fi + r], sj = first ? sj0 : gmem(P.sF)[(size_t)R.fj + q];
     double H = 0.0;
     if (nc <= kSbPre) {
       double v[kSbPre];
@@ -1181,18 +1203,15 @@ __device__ __forceinline__ void asmPairsSb(const DevProblem& P, int bid) {
     }
     double val = si * sj * H;
     if (diag && r == q) {
-      const size_t idx = (size_t)foff + offi + r;
-      const double dg = sqrt(fmin(fmax(si * si * gmem(P.hdF)[idx], P.opt.min_lm_diagonal), P.opt.max_lm_diagonal));
+      const size_t idx = (size_t)R.fi + r;
+      const double hd = first ? hd0 : gmem(P.hdF)[idx];
+      const double dg = sqrt(fmin(fmax(si * si * hd, P.opt.min_lm_diagonal), P.opt.max_lm_diagonal));
       gmemw(P.diagF)[idx] = dg;
-      const double d = dg * smu;
-      val += d * d;
+      val = asmDamped(val, dg * smu);
     }
-    S[(int64_t)(offi + r) * ld + offj + q] = val;
+    S[(int64_t)r * ld + q] = val;
   }
-  if (diag && lane < ni) {
-    const size_t idx = (size_t)foff + offi + lane;
-    gmemw(P.rhsF)[idx] = gmem(P.sF)[idx] * gmem(P.gF)[idx];
-  }
+  if (diag && lane < ni) gmemw(P.rhsF)[(size_t)R.fi + lane] = sl0 * gl0;
 }
 __global__ __launch_bounds__(256) void k_assemble_sb(const DevProblem* __restrict__ Pp) { asmPairsSb(*Pp, (int)blockIdx.x); }
 

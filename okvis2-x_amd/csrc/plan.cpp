@@ -10,6 +10,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <numeric>
 #include <stdexcept>
 
@@ -1181,6 +1182,28 @@ void closeBatch(HostBatch& B) {
 
 }  // namespace
 
+std::vector<AsmRec> assemblyRecords(const HostBatch& B) {
+  std::vector<AsmRec> out;
+  out.reserve(B.asm_pp_items.size() + B.asm_ppl_items.size() + B.asm_sb_items.size());
+  for (const auto* list : {&B.asm_pp_items, &B.asm_ppl_items, &B.asm_sb_items})
+    for (const int32_t k : *list) {
+      AsmRec r{};
+      r.win = -1;  // pad item: every other field 0 (clamped loads of a pad stay inside the arrays)
+      if (k >= 0) {
+        const int w = B.pair_win[k], fi = B.pair_fi[k], fj = B.pair_fj[k];
+        r.win = w;
+        r.cb = B.pair_cbegin[k]; r.pb = B.pair_runs[2 * (size_t)k]; r.ob = B.pair_runs[2 * (size_t)k + 1];
+        r.ce = B.pair_cbegin[(size_t)k + 1];
+        r.fi = B.win_foff[w] + B.fb_off[fi]; r.fj = B.win_foff[w] + B.fb_off[fj];
+        r.ld = B.win_fpad[w];
+        r.dst = B.win_soff[w] + (int64_t)B.fb_off[fi] * B.win_fpad[w] + B.fb_off[fj];
+        r.flags = (fi == fj ? 1 : 0) | (B.fb_kind[fi] != 0 ? 2 : 0) | (B.fb_kind[fj] != 0 ? 4 : 0);
+      }
+      out.push_back(r);
+    }
+  return out;
+}
+
 void analyse(const std::vector<const okvisgpu_problem*>& probs,
              const std::map<std::tuple<int, int, int>, int>& constOverride, HostBatch& B) {
   B.seg_gbegin.push_back(0);
@@ -1221,6 +1244,7 @@ void analyse(const std::vector<const okvisgpu_problem*>& probs,
   cholLaunchItems(B);
   assemblyLists(B);
   closeBatch(B);
+  B.asm_rec = assemblyRecords(B);  // (after closeBatch: the closing entry of pair_cbegin)
   ATIME(12)
 }
 
@@ -1360,6 +1384,49 @@ extern "C" int okvisgpu_plan_digest(const okvisgpu_problem* problems, int32_t n_
       for (size_t k = 0; k < b.bytes; ++k) h = (h ^ c[k]) * 1099511628211ull;
       hash[i] = h;
     }
+    return OKVISGPU_OK;
+  } catch (const UnsupportedError&) {
+    return OKVISGPU_ERR_UNSUPPORTED;
+  } catch (const std::exception&) {
+    return OKVISGPU_ERR_INVALID_ARGUMENT;
+  } catch (const ArgError&) {
+    return OKVISGPU_ERR_INVALID_ARGUMENT;
+  }
+}
+
+// ---- okvisgpu_plan_assembly (okvisgpu.h): the assembly records beside the arrays they restate ------
+extern "C" int okvisgpu_plan_assembly(const okvisgpu_problem* problems, int32_t n_windows, int32_t cu_count,
+                                      int32_t* counts, int32_t capacity, int32_t* records, int64_t* arrays) {
+  using namespace okg;
+  if (!problems || n_windows <= 0 || !counts) return OKVISGPU_ERR_INVALID_ARGUMENT;
+  try {
+    std::vector<const okvisgpu_problem*> probs;
+    for (int i = 0; i < n_windows; ++i) probs.push_back(&problems[i]);
+    HostBatch B;
+    B.opt = planOptions(n_windows, cu_count);
+    analyse(probs, {}, B);
+    counts[0] = (int32_t)B.asm_pp_items.size(); counts[1] = (int32_t)B.asm_ppl_items.size();
+    counts[2] = (int32_t)B.asm_sb_items.size(); counts[3] = (int32_t)B.asm_rec.size();
+    static_assert(sizeof(AsmRec) == kAsmRecInts * sizeof(int32_t), "records are copied out as int32");
+    int n = 0;
+    for (const auto* list : {&B.asm_pp_items, &B.asm_ppl_items, &B.asm_sb_items})
+      for (const int32_t k : *list) {
+        if (n >= capacity) return OKVISGPU_OK;
+        if (records && n < (int)B.asm_rec.size()) std::memcpy(records + kAsmRecInts * (size_t)n, &B.asm_rec[n], sizeof(AsmRec));
+        if (arrays) {  // what a kernel reached from the item through the separate arrays
+          int64_t* a = arrays + 16 * (size_t)n;
+          std::fill(a, a + 16, 0);
+          a[0] = k;
+          if (k >= 0) {
+            const int w = B.pair_win[k], fi = B.pair_fi[k], fj = B.pair_fj[k];
+            const int64_t v[16] = {k, w, B.pair_cbegin[k], B.pair_runs[2 * (size_t)k], B.pair_runs[2 * (size_t)k + 1],
+                                   B.pair_cbegin[(size_t)k + 1], fi, fj, B.fb_off[fi], B.fb_off[fj], B.fb_kind[fi],
+                                   B.fb_kind[fj], B.win_foff[w], B.win_fpad[w], B.win_soff[w], 0};
+            std::copy(v, v + 16, a);
+          }
+        }
+        ++n;
+      }
     return OKVISGPU_OK;
   } catch (const UnsupportedError&) {
     return OKVISGPU_ERR_UNSUPPORTED;

@@ -129,6 +129,9 @@ struct HostBatch {
   std::vector<Contrib> fb_contrib;
   std::vector<int32_t> pair_win, pair_fi, pair_fj, pair_cbegin, pair_runs;
   std::vector<int32_t> asm_pp_items, asm_sb_items, asm_ppl_items;
+  // the three lists item by item as AsmRec records (heavy, light, speed/bias; assemblyRecords).
+  // Not an arena-table entry: the runtime uploads it into a buffer of its own.
+  std::vector<AsmRec> asm_rec;
   std::vector<int32_t> chol_upd_items, chol_upd_begin, tile_items;
   int64_t n_panels = 0;  // structurally non-zero tiles below the diagonal (panel products)
   int64_t n_band_updates = 0;
@@ -153,6 +156,11 @@ int cholSchedule(const std::vector<uint8_t>& nz, int T, std::vector<int>& L, std
 // okvisgpu_set_block_constant() edits. Throws ArgError / UnsupportedError on a bad problem.
 void analyse(const std::vector<const okvisgpu_problem*>& probs,
              const std::map<std::tuple<int, int, int>, int>& constOverride, HostBatch& B);
+
+// The record of every assembly work item (B.asm_pp_items, then B.asm_ppl_items, then
+// B.asm_sb_items), from the batch's pair, block and window arrays. Pure: reads B, returns the records
+// (analyse() keeps them in B.asm_rec).
+std::vector<AsmRec> assemblyRecords(const HostBatch& B);
 
 // Development: host-time split of analyse() by phase (build with -DOKG_ANALYSE_TIMING; printed by
 // okvisgpu_plan_window): validate, params, flags, state order, observation sort, visits, extrinsic

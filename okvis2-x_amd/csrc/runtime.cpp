@@ -225,6 +225,10 @@ struct okvisgpu_ctx {
   // tables | per-keypoint outputs): likewise
   void* matchScratch = nullptr;
   size_t matchScratchBytes = 0;
+  // the assembly work items as records (HostBatch::asm_rec, DevProblem::asm_rec): likewise outside
+  // the arena table, uploaded by build(), grown as needed
+  void* asmRecBuf = nullptr;
+  size_t asmRecBytes = 0;
 
   void fillSummaries(const std::vector<WinState>& st, okvisgpu_summary* sums) {
     if (!sums) return;
@@ -285,6 +289,7 @@ struct okvisgpu_ctx {
     if (lmScratch) (void)hipFree(lmScratch);
     if (covisScratch) (void)hipFree(covisScratch);
     if (propScratch) (void)hipFree(propScratch);
+    if (asmRecBuf) (void)hipFree(asmRecBuf);
     if (matchScratch) (void)hipFree(matchScratch);
     for (hipEvent_t e : forkEv) (void)hipEventDestroy(e);
     for (hipStream_t q : side)
@@ -531,6 +536,19 @@ struct okvisgpu_ctx {
     sNeedsInit = true;
     L.patch(base);
     P.gL = P.lm_g;  // the landmark gradient is the accumulated J_l^T r
+    {  // the assembly records: the context's own buffer (not an arena-table entry)
+      const size_t need = std::max<size_t>(sizeof(AsmRec), B.asm_rec.size() * sizeof(AsmRec));
+      if (need > asmRecBytes) {
+        if (asmRecBuf) HIPCHK(hipFree(asmRecBuf));
+        asmRecBuf = nullptr;
+        asmRecBytes = 0;
+        HIPCHK(hipMalloc(&asmRecBuf, need));
+        asmRecBytes = need;
+      }
+      if (!B.asm_rec.empty())
+        HIPCHK(hipMemcpyAsync(asmRecBuf, B.asm_rec.data(), B.asm_rec.size() * sizeof(AsmRec), hipMemcpyHostToDevice, stream));
+      P.asm_rec = static_cast<const AsmRec*>(asmRecBuf);
+    }
     HIPCHK(hipStreamSynchronize(stream));
     decideRegime(0);  // (default options: the entry points that launch without a solve_begin)
     uploadDescriptor();

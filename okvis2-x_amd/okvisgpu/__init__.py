@@ -255,7 +255,7 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_eval_host", "okvisgpu_plan_window", "okvisgpu_loss_evaluate", "okvisgpu_plan_digest",
     "okvisgpu_launch_regime", "okvisgpu_update_landmarks", "okvisgpu_covisibilities", "okvisgpu_imu_propagate",
     "okvisgpu_twopose_extrinsics_compute", "okvisgpu_twopose_extrinsics_evaluate", "okvisgpu_gauss_newton_step",
-    "okvisgpu_match_to_map",
+    "okvisgpu_match_to_map", "okvisgpu_plan_assembly",
 ]
 N_PHASES = 15
 TWOPOSE_MAX_CAMERAS = 6
@@ -320,6 +320,7 @@ def lib():
         L.okvisgpu_plan_digest.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, _lp, C.c_int32, _ip, C.c_char_p,
                                            _ip, _lp, C.POINTER(C.c_uint64)]
         L.okvisgpu_launch_regime.argtypes = [C.c_int32] * 9 + [_ip]
+        L.okvisgpu_plan_assembly.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, _ip, C.c_int32, _ip, _lp]
         L.okvisgpu_imu_append.argtypes = [C.c_void_p, C.POINTER(ImuAppendBatch), _ip]
         L.okvisgpu_imu_propagate.argtypes = [C.c_void_p, C.POINTER(ImuPropagateBatch), _ip]
         L.okvisgpu_match_to_map.argtypes = [C.c_void_p, C.POINTER(MatchBatch), C.POINTER(MatchResult)]
@@ -384,6 +385,24 @@ def plan_digest(problems, cu_count):
     entries = [[names.raw[32 * i:32 * i + 32].split(b"\0")[0].decode(), int(region[i]), int(nbytes[i]),
                 f"{hashes[i]:016x}" if region[i] == 0 else None] for i in range(cap)]
     return {"totals": {k: int(v) for k, v in zip(PLAN_DIGEST_TOTALS, totals)}, "entries": entries}
+
+
+def plan_assembly(problems, cu_count):
+    """okvisgpu_plan_assembly (host only): (counts of the heavy / light / speed-bias item lists,
+    records [n][12] int32, arrays [n][16] int64) of a batch's plan on a device of cu_count CUs."""
+    L = lib()
+    arr = (Problem * len(problems))(*problems)
+    counts = (C.c_int32 * 4)()
+    rc = L.okvisgpu_plan_assembly(arr, len(problems), int(cu_count), counts, 0, None, None)
+    if rc != 0:
+        raise RuntimeError(f"okvisgpu_plan_assembly failed ({rc})")
+    n = int(counts[3])
+    rec, old = np.zeros((max(n, 1), 12), np.int32), np.zeros((max(n, 1), 16), np.int64)
+    rc = L.okvisgpu_plan_assembly(arr, len(problems), int(cu_count), counts, n, rec.ctypes.data_as(_ip),
+                                  old.ctypes.data_as(_lp))
+    if rc != 0 or int(counts[3]) != n:
+        raise RuntimeError(f"okvisgpu_plan_assembly failed ({rc})")
+    return [int(c) for c in counts[:3]], rec[:n], old[:n]
 
 
 LAUNCH_REGIME = ("few", "many", "serial_graph", "lin_prep", "fused_gradnorm", "graph_iters", "chol_schedule")
