@@ -320,11 +320,12 @@ struct DevProblem {
   double* hdF;                     // unscaled diag(H_ff)
   double* gF;   double* gL;        // unscaled gradient J^T r
   double* rhsF;                    // Schur rhs / forward-substitution workspace
-  double* yF;   double* yL;        // GN solution (Jacobi-scaled space)
+  double* yF;   double* yL;        // GN solution (Jacobi-scaled space); yL is stored only for
+                                   //   okvisgpu_gauss_newton_step, the iteration does not read it
   double* gnF;  double* gnL;       // gauss_newton_step_ (dogleg-scaled)
   double* dgF;  double* dgL;       // gradient_ (dogleg-scaled)
-  double* vF;   double* vL;        // J*v operand (Jacobi-scaled space)
-  double* stepF; double* stepL;    // trust-region step (Jacobi-scaled space)
+  double* vF;   double* vL;        // J*v operand (Jacobi-scaled space); vL unused in the loop (never stored)
+  double* stepF; double* stepL;    // trust-region step: unused in the loop (never stored; the arena keeps them)
 
   WinState* st;                    // [n_win]
   DevOptions opt;

@@ -32,7 +32,11 @@ __device__ __forceinline__ void jvAcc(double jc, double jg, double (&a)[3]) {
 // One 16-lane group per factor (IMU factor, pose prior, speed/bias prior, relative-pose edge, in
 // that order), lane = residual row: J_s v_c and J_s v_g of its row over the factor's free blocks,
 // then (jc^2, jg^2, jc jg) summed over the rows by a fixed shuffle tree.
-__device__ __forceinline__ void jvGroups(const DevProblem& P, int block) {
+// sVc: the workgroup's LDS for the IMU factors' direction vectors (the caller's, so that
+// k_lm_backsub_jv can lend it the storage of its observation stage).
+using JvLds = double[32][2];
+constexpr int kJvLdsGroups = 256 / 16;
+__device__ __forceinline__ void jvGroups(const DevProblem& P, int block, JvLds* sVc) {
   const int gid = (block * 256 + (int)threadIdx.x) >> 4, r = threadIdx.x & 15;
   const double* __restrict__ cF = P.vF;
   const double* __restrict__ yF = P.yF;
@@ -45,7 +49,6 @@ __device__ __forceinline__ void jvGroups(const DevProblem& P, int block) {
   // IMU factors (the bulk): every operand in three rounds of loads, no branch on a loaded value
   // before they are issued. Lane r holds row r of the 15x30 Jacobian; lanes r and r + 16 of the
   // group form the scaled direction vectors of columns r and r + 16, exchanged through LDS.
-  __shared__ double sVc[256 / 16][32][2];
   if (gid < P.n_fac) {
     const int f = gid, grp = threadIdx.x >> 4;
     const int fw = gmem(P.imu_win)[f], ffl = gmem(P.imu_flags)[f];

@@ -352,7 +352,6 @@ __global__ __launch_bounds__(RB) void k_dogleg(const DevProblem* __restrict__ Pp
       const double v = ca * dg[c] + cb * gn[c];
       dn2 += v * v;
       const double st = v / dia[c];
-      gmemw(P.stepF)[(size_t)foff + pf + c] = st;
       delta[c] = st * sc[c];
       jr += delta[c] * g[c];
     }
@@ -384,7 +383,6 @@ __global__ __launch_bounds__(RB) void k_dogleg(const DevProblem* __restrict__ Pp
       const double v = ca * dg[c] + cb * gn[c];
       dn2 += v * v;
       const double st = v / dia[c];
-      gmemw(P.stepF)[(size_t)foff + sf + c] = st;
       jr += (st * sc[c]) * g[c];
       const double yv = x[c] + st * sc[c];
       y[c] = yv;
@@ -415,7 +413,6 @@ __global__ __launch_bounds__(RB) void k_dogleg(const DevProblem* __restrict__ Pp
                         const double vv = ca * v.dg[c] + cb * v.gn[c];
                         dn2 += vv * vv;
                         const double st = vv / v.dia[c];
-                        gmemw(P.stepL)[3 * (size_t)l + c] = st;
                         jr += (st * v.sl[c]) * v.g[c];
                         const double yv = v.x[c] + st * v.sl[c];
                         y[c] = yv;
@@ -464,7 +461,10 @@ __global__ __launch_bounds__(RB) void k_dogleg(const DevProblem* __restrict__ Pp
 
 // The factors' J*v on their own: in the iteration they are the trailing workgroups of
 // k_lm_backsub_jv (launch_lm_backsub); this launch serves okvisgpu_time_kernel's table.
-__global__ __launch_bounds__(256) void k_jv(const DevProblem* __restrict__ Pp) { jvGroups(*Pp, (int)blockIdx.x); }
+__global__ __launch_bounds__(256) void k_jv(const DevProblem* __restrict__ Pp) {
+  __shared__ double sVc[kJvLdsGroups][32][2];
+  jvGroups(*Pp, (int)blockIdx.x, sVc);
+}
 void launch_jv(const DevProblem& P, hipStream_t s) {
   if (jvBlocks(P) > 0) hipLaunchKernelGGL(k_jv, dim3(jvBlocks(P)), dim3(256), 0, s, P.self);
 }

@@ -56,7 +56,8 @@ void launch_lm_prep(const DevProblem& P, hipStream_t s);
 void launch_lin_few(const DevProblem& P, hipStream_t s);
 void launch_zero_S(const DevProblem& P, hipStream_t s);  // the non-zero tiles of S, once per build
 void launch_assemble(const DevProblem& P, hipStream_t s);  // few: one launch, else pp + sb
-void launch_lm_backsub(const DevProblem& P, hipStream_t s);  // kernels_backsub.hip: + landmark dogleg vectors, J*v
+void launch_lm_backsub(const DevProblem& P, hipStream_t s, bool storeY = false);  // kernels_backsub.hip: + landmark dogleg
+                                                                               // vectors, J*v; storeY: y_l too
 void launch_assemble_gradnorm_few(const DevProblem& P, hipStream_t s);  // few windows: + the gradient test
 void launch_assemble_pp(const DevProblem& P, hipStream_t s);
 void launch_assemble_sb(const DevProblem& P, hipStream_t s);

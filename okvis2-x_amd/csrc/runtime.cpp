@@ -1392,9 +1392,10 @@ double kernelWork(const HostBatch& B, const DevProblem& P, int k) {
       return nImu * (kImuLin + 3) * d8 + (double)P.n_pprior * (42 + 3) * d8 + (double)P.n_sbprior * (90 + 3) * d8 +
              (double)P.n_relpose * (kRelPoseLin + 3) * d8;
     case K_LM_BACKSUB:  // obs linearisation (A, flags) once; pose / landmark parameters and vectors once per
-                        // block; landmark step + dogleg vectors and the visits' J*v forms out
+                        // block; gauss_newton_step_ and gradient_ of the landmarks (6 doubles) and the
+                        // groups' J*v forms out
       return nObs * (6 * d8 + 1) + nVis * (3 * d8 + 16) + (double)P.n_pose * (7 + 18) * d8 +
-             nLm * (4 + 9 + 3 + 3 + 3 + 3 + 12) * d8;
+             nLm * (4 + 9 + 3 + 3 + 3 + 3 + 6) * d8 + (double)P.n_lmg * kGrpRed * d8;
     case K_FGRAD: return (double)P.n_seg * 27 * d8 + nImu * kImuLin * d8 + (double)B.fb_contrib.size() * 16;
   }
   return 0.0;
@@ -1653,7 +1654,7 @@ int okvisgpu_gauss_newton_step(okvisgpu_ctx* c, int32_t window, const okvisgpu_o
     launch_lm_prep(c->P, c->stream);
     launch_assemble(c->P, c->stream);
     launch_cholesky(c->P, c->stream);
-    launch_lm_backsub(c->P, c->stream);
+    launch_lm_backsub(c->P, c->stream, /*storeY=*/true);  // (y_l is stored for this entry point only)
     HIPCHK(hipGetLastError());
     auto st = c->readStates();
     const HostBatch& B = c->B;
