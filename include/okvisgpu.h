@@ -636,6 +636,101 @@ typedef struct okvisgpu_match_result {  /* caller-owned, any may be NULL */
 } okvisgpu_match_result;
 int okvisgpu_match_to_map(okvisgpu_ctx* ctx, const okvisgpu_match_batch* batch, okvisgpu_match_result* result);
 
+/* ---------------------------------------------------------------- frame-to-frame matching
+ * (An addition to ABI 6: a new entry point and two new structs; OKVISGPU_ABI_VERSION stays 6.)
+ * The keypoint-against-keypoint BRISK matching of Frontend::matchMotionStereo's worker loop
+ * (okvis_frontend/src/Frontend.cpp:2057-2149) and of Frontend::matchStereo's inner loop (:2259-2316) on
+ * the GPU, with triangulateFast (stereo_triangulation.cpp:30-112). One batch is n_jobs independent jobs;
+ * a job matches the keypoints of image 0 ("side 0", suffix 0) against those of image 1 ("side 1",
+ * suffix 1) in one mode: 0 = motion stereo (side 0 an older keyframe's image `im`, side 1 the current
+ * frame's image `im`; job_camera0 = job_camera1 = im), 1 = stereo (two images of one multiframe;
+ * job_pose0 = job_pose1). The keypoints of each side are stored job after job (kp0_begin / kp1_begin).
+ * normalised(v) below is v / |v| for |v|^2 > 0 and v otherwise (Eigen).
+ *
+ * Both modes, per job: T_WCi = job_pose_i job_extrinsics_i (C_WCi, r_WCi), f_i = (fu + fv) / 2 of camera
+ * job_camera_i; per keypoint e_W = normalised(C_WCi ray). depth_i(p) = (C_WCi^T (p - r_WCi))_z.
+ * A side-0 keypoint k0 walks the side-1 keypoints of its job that have use1 != 0, in ascending index,
+ * with a running `best`; a candidate k1 whose Hamming distance over the 48 bytes is < best is tested
+ * for admissibility and, if admissible, becomes the record: best = its distance, match = k1, point =
+ * [p, 1] with p the triangulated point, initialisable = triangulateFast did not report parallel.
+ *
+ * Mode 0 (:2057-2149). k0 takes part iff use0 and ray_valid0; use0 is the caller's fold of the
+ * landmarkId / isLandmarkAdded / isLandmarkInitialised / isObserved rules (:2058-2066, :2085) and use1
+ * "carries no landmark" (:2037-2041). sigma = size0 / f0 * 0.125. best starts at matching_threshold
+ * truncated to an unsigned integer (uint32_t distances = briskMatchingThreshold_). A candidate is
+ * admissible iff ray_valid1, e0 . e1 >= 0.5, triangulateFast(r_WC0, e0, r_WC1, e1, sigma) is valid,
+ * e0 . e1 >= 0.8, depth_0(p) >= 0.2 and depth_1(p) >= 0.2 (each written as "not <", so a NaN passes, as
+ * in the reference). The record also holds quality = acos(normalised(p - r_WC0) . normalised(p -
+ * r_WC1)) in plain IEEE arithmetic (a rounded argument above 1 gives NaN, as in the reference). After
+ * the walk the record is kept only if best < matching_threshold (as doubles) and projectHomogeneous(
+ * camera1, T_WC1^-1 point) is Successful (|z| >= 1e-12; radtan8: rho <= 9; inside [0, width) x [0,
+ * height); z > 0; no mask) and lands less than 4.0 px from keypoint1 (:2140-2147). If that check fails
+ * the keypoint has no match: there is no fall-back to another candidate.
+ * Mode 1 (:2259-2316). k0 takes part iff use0. best starts at matching_threshold as a double. A
+ * candidate is admissible iff ray_valid0, ray_valid1, triangulateFast valid with sigma = max(size0 /
+ * f0, size1 / f1) * 0.125, depth_0(p) >= 0.1, depth_1(p) >= 0.1 and e0 . e1 >= 0.8. quality is 0 and
+ * there is no final projection test. What follows in the reference (:2318-2387: merge, setLandmark,
+ * addLandmark and the two 4-px checks against the estimator's point) reads and mutates estimator state
+ * and stays with the caller, as does the insertion loop of mode 0 (:2159-2201).
+ * In both modes admissibility does not depend on best, so the result equals the serial walk's and is
+ * independent of the reference's thread count: the match is the first admissible side-1 keypoint
+ * attaining the minimum admissible distance below the threshold; point, initialisable and quality are
+ * that candidate's.
+ *
+ * Results are indexed by side-0 keypoint; a keypoint without a match (or not taking part) gets match
+ * -1, distance -1, point 0, initialisable 0, quality 0. `match` is the side-1 index within the job
+ * (0 .. kp1_begin[j+1] - kp1_begin[j] - 1).
+ *
+ * Independent of the problem set with okvisgpu_set_problems (needs none, leaves the device parameter
+ * sets alone); uses the context's device and stream and returns with the results in the caller's
+ * arrays. A job's result does not depend on the other jobs of the batch and is the same bits on every
+ * run. n_jobs = 0, a job with an empty side 0 or side 1 and all-zero use arrays are valid (empty / -1
+ * outputs). OKVISGPU_ERR_INVALID_ARGUMENT, before anything is launched or written, for a NULL ctx,
+ * batch or result, missing arrays, negative counts, a CSR array not starting at 0 or not monotone, a
+ * camera index or a mode out of range, and between okvisgpu_solve_begin and _solve_end;
+ * okvisgpu_last_error names the offender. */
+typedef struct okvisgpu_frame_match_batch {
+  /* --- shared */
+  int32_t n_cameras;
+  const okvisgpu_camera* cameras;   /* [n_cameras]                                                 */
+  double matching_threshold;        /* briskMatchingThreshold_, 60.0 in the reference              */
+  /* --- jobs */
+  int32_t n_jobs;
+  const int32_t* job_mode;          /* [n_jobs] 0 = motion stereo, 1 = stereo                      */
+  const int32_t* job_camera0;       /* [n_jobs] intrinsics of side 0                               */
+  const int32_t* job_camera1;       /* [n_jobs] intrinsics of side 1 (mode 0: the same camera)     */
+  const double* job_pose0;          /* [n_jobs][7] T_WS of side 0's frame                          */
+  const double* job_pose1;          /* [n_jobs][7] T_WS of side 1's frame (mode 1: the same pose)  */
+  const double* job_extrinsics0;    /* [n_jobs][7] T_SC of side 0 (mode 0: the older state's, :2021) */
+  const double* job_extrinsics1;    /* [n_jobs][7] T_SC of side 1 (mode 0: the current state's, :2022) */
+  const int32_t* kp0_begin;         /* [n_jobs+1] CSR into the side-0 keypoint arrays              */
+  const int32_t* kp1_begin;         /* [n_jobs+1] CSR into the side-1 keypoint arrays              */
+  /* --- side-0 keypoints */
+  const double* keypoint0;          /* [n_kp0][2] (not read by the matching: for symmetry, may be NULL) */
+  const double* size0;              /* [n_kp0]    getKeypointSize                                  */
+  const uint8_t* descriptor0;       /* [n_kp0][48]                                                 */
+  const double* ray0;               /* [n_kp0][3] getBackProjection, not normalised ...            */
+  const uint8_t* ray_valid0;        /* [n_kp0]    ... and its bool                                 */
+  const uint8_t* use0;              /* [n_kp0]    NULL = all 1                                     */
+  /* --- side-1 keypoints */
+  const double* keypoint1;          /* [n_kp1][2]                                                  */
+  const double* size1;              /* [n_kp1]                                                     */
+  const uint8_t* descriptor1;       /* [n_kp1][48]                                                 */
+  const double* ray1;               /* [n_kp1][3]                                                  */
+  const uint8_t* ray_valid1;        /* [n_kp1]                                                     */
+  const uint8_t* use1;              /* [n_kp1]    NULL = all 1                                     */
+} okvisgpu_frame_match_batch;
+
+typedef struct okvisgpu_frame_match_result {  /* caller-owned, any may be NULL; all [n_kp0] */
+  int32_t* match;                   /* side-1 keypoint index within the job, -1 = none             */
+  int32_t* distance;                /* Hamming distance of the match, -1 = none                    */
+  double* point;                    /* [n_kp0][4] hp_W = [p, 1], 0 without a match                 */
+  uint8_t* initialisable;           /* 1 = the match's triangulation is not parallel               */
+  double* quality;                  /* mode 0: the parallax angle of the match; mode 1: 0          */
+} okvisgpu_frame_match_result;
+int okvisgpu_match_frames(okvisgpu_ctx* ctx, const okvisgpu_frame_match_batch* batch,
+                          okvisgpu_frame_match_result* result);
+
 /* ---------------------------------------------------------------- post-solve landmark pass
  * (An addition to ABI 6: a new entry point and a new struct; no existing struct or call changes, so
  * OKVISGPU_ABI_VERSION stays 6 and a caller built against the earlier header keeps working.)

@@ -437,4 +437,47 @@ struct MatchDev {
   double* out_point;              // [n_kp][4]
 };
 
+// Frontend::matchMotionStereo / matchStereo for a batch of jobs (okvisgpu_frame_match_batch on device;
+// kernels_match_frames.hip). Camera rows as MatchDev's. A job's row of job_geo, written by the prepare
+// kernel: C_WC0 [9] row-major, r_WC0 [3], C_WC1 [9], r_WC1 [3], f0, f1 (the mean focal lengths).
+constexpr int kFrameGeoDoubles = 26;
+struct FrameMatchDev {
+  int32_t n_jobs, n_kp0, n_kp1;
+  int32_t n_list0, n_list1;       // participating side-0 keypoints of the mode-0 / mode-1 jobs
+  // best's start as an integer: a Hamming distance d is below the threshold iff d < best_init[mode]
+  // (mode 0: the threshold truncated, mode 1: its ceiling; both clamped to [0, 385])
+  int32_t best_init[2];
+  const double* cam;              // [n_cam][kMatchCamDoubles]
+  const int32_t* job_cam0;        // [n_jobs]
+  const int32_t* job_cam1;        // [n_jobs]
+  const double* job_pose0;        // [n_jobs][7]
+  const double* job_pose1;        // [n_jobs][7]
+  const double* job_ext0;         // [n_jobs][7]
+  const double* job_ext1;         // [n_jobs][7]
+  const int32_t* kp1_begin;       // [n_jobs+1]
+  const int32_t* kp0_job;         // [n_kp0]
+  const int32_t* kp1_job;         // [n_kp1]
+  const int32_t* kp_list;         // [n_list0 + n_list1] side-0 keypoints, the mode-0 jobs' first
+  const double* size0;            // [n_kp0]
+  const uint32_t* desc0;          // [n_kp0][12]
+  const double* ray0;             // [n_kp0][3]
+  const double* xy1;              // [n_kp1][2]
+  const double* size1;            // [n_kp1]
+  const uint32_t* desc1;          // [n_kp1][12]
+  const double* ray1;             // [n_kp1][3]
+  const uint8_t* valid1;          // [n_kp1]
+  const uint8_t* use1;            // [n_kp1] or nullptr (all)
+  // written by the prepare kernel, read by the match kernels
+  double* job_geo;                // [n_jobs][kFrameGeoDoubles]
+  double* e0;                     // [n_kp0][3] e_W
+  double* e1;                     // [n_kp1][3]
+  uint8_t* flag1;                 // [n_kp1] use1 && ray_valid1
+  // per side-0 keypoint
+  int32_t* out_match;
+  int32_t* out_dist;
+  double* out_point;              // [n_kp0][4]
+  double* out_quality;
+  uint8_t* out_init;
+};
+
 }  // namespace okg

@@ -94,6 +94,13 @@ void launch_twopose_extr_eval(const TwoPoseExtrEvalDev& T, hipStream_t s);
 void launch_match_prepare(const MatchDev& M, hipStream_t s);
 void launch_match(const MatchDev& M, hipStream_t s);
 
+// Frontend::matchMotionStereo / matchStereo (kernels_match_frames.hip; okvisgpu_match_frames): one lane
+// per keypoint of either side and per job (rays in W, side 1's flag, the jobs' transforms; every
+// per-keypoint output gets its no-match value), then one wavefront per participating side-0 keypoint
+// of the mode-0 and of the mode-1 jobs.
+void launch_match_frames_prepare(const FrameMatchDev& F, hipStream_t s);
+void launch_match_frames(const FrameMatchDev& F, hipStream_t s);
+
 // post-solve landmark pass (kernels_landmarks.hip): ViGraph::updateLandmarks on parameter set 0 (run
 // launch_select_current first), one lane per landmark. Outputs in device order: quality [n_lm],
 // flags [n_lm] (kLmInitialised | kLmReset | kLmNotInFront), obs_err [n_obs]; dirs [n_obs][3] is

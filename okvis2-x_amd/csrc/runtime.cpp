@@ -225,6 +225,10 @@ struct okvisgpu_ctx {
   // tables | per-keypoint outputs): likewise
   void* matchScratch = nullptr;
   size_t matchScratchBytes = 0;
+  // okvisgpu_match_frames' device arrays (cameras | jobs | lists | keypoints of both sides || per-keypoint
+  // outputs || rays in W, flags, job transforms): likewise
+  void* frameMatchScratch = nullptr;
+  size_t frameMatchScratchBytes = 0;
   // the assembly work items as records (HostBatch::asm_rec, DevProblem::asm_rec): likewise outside
   // the arena table, uploaded by build(), grown as needed
   void* asmRecBuf = nullptr;
@@ -291,6 +295,7 @@ struct okvisgpu_ctx {
     if (propScratch) (void)hipFree(propScratch);
     if (asmRecBuf) (void)hipFree(asmRecBuf);
     if (matchScratch) (void)hipFree(matchScratch);
+    if (frameMatchScratch) (void)hipFree(frameMatchScratch);
     for (hipEvent_t e : forkEv) (void)hipEventDestroy(e);
     for (hipStream_t q : side)
       if (q) (void)hipStreamDestroy(q);
@@ -2104,6 +2109,169 @@ int okvisgpu_match_to_map(okvisgpu_ctx* c, const okvisgpu_match_batch* A, okvisg
     get(R->n_records, o_r, 4 * nk);
     get(R->record_repr_sum, o_s, 8 * nk);
     get(R->point, o_pt, 32 * nk);
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_match_frames(okvisgpu_ctx* c, const okvisgpu_frame_match_batch* A, okvisgpu_frame_match_result* R) {
+  if (!c || !A || !R) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_frames: bad arguments");
+  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_frames: call after solve_end");
+  if (A->n_jobs < 0 || A->n_cameras < 0) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_frames: negative count");
+  if (A->n_jobs == 0) return OKVISGPU_OK;
+  return guarded(c, [&]() {
+    const std::string who = "match_frames: ";
+    const size_t nj = (size_t)A->n_jobs, nc = (size_t)A->n_cameras;
+    if (!A->job_mode || !A->job_camera0 || !A->job_camera1 || !A->job_pose0 || !A->job_pose1 || !A->job_extrinsics0 ||
+        !A->job_extrinsics1 || !A->kp0_begin || !A->kp1_begin)
+      throw ArgError{who + "job arrays missing"};
+    if (!nc || !A->cameras) throw ArgError{who + "cameras missing"};
+    if (A->kp0_begin[0] != 0) throw ArgError{who + "kp0_begin must start at 0"};
+    if (A->kp1_begin[0] != 0) throw ArgError{who + "kp1_begin must start at 0"};
+    for (size_t j = 0; j < nj; ++j) {
+      if (A->kp0_begin[j + 1] < A->kp0_begin[j]) throw ArgError{who + "kp0_begin not monotone at job " + std::to_string(j)};
+      if (A->kp1_begin[j + 1] < A->kp1_begin[j]) throw ArgError{who + "kp1_begin not monotone at job " + std::to_string(j)};
+    }
+    const size_t n0 = (size_t)A->kp0_begin[nj], n1 = (size_t)A->kp1_begin[nj];
+    if (n0 && (!A->size0 || !A->descriptor0 || !A->ray0 || !A->ray_valid0)) throw ArgError{who + "side-0 keypoint arrays missing"};
+    if (n1 && (!A->keypoint1 || !A->size1 || !A->descriptor1 || !A->ray1 || !A->ray_valid1))
+      throw ArgError{who + "side-1 keypoint arrays missing"};
+    for (size_t j = 0; j < nj; ++j) {
+      if (A->job_mode[j] != 0 && A->job_mode[j] != 1) throw ArgError{who + "job_mode not 0 / 1 at job " + std::to_string(j)};
+      if (A->job_camera0[j] < 0 || A->job_camera0[j] >= A->n_cameras)
+        throw ArgError{who + "job_camera0 out of range at job " + std::to_string(j)};
+      if (A->job_camera1[j] < 0 || A->job_camera1[j] >= A->n_cameras)
+        throw ArgError{who + "job_camera1 out of range at job " + std::to_string(j)};
+    }
+    std::vector<double> cam((size_t)kMatchCamDoubles * nc);
+    for (size_t k = 0; k < nc; ++k) {
+      const okvisgpu_camera& q = A->cameras[k];
+      if (q.distortion < 0 || q.distortion > 3) throw ArgError{who + "unknown distortion model of camera " + std::to_string(k)};
+      const double cv[kMatchCamDoubles] = {(double)q.distortion, q.fu, q.fv, q.cu, q.cv, q.dist[0], q.dist[1], q.dist[2],
+                                           q.dist[3], q.dist[4], q.dist[5], q.dist[6], q.dist[7], (double)q.width,
+                                           (double)q.height};
+      std::memcpy(&cam[kMatchCamDoubles * k], cv, sizeof(cv));
+    }
+    // the side-0 keypoints that take part (use0 and ray_valid0: in mode 1 a keypoint without a valid ray
+    // has no admissible candidate), per mode
+    size_t nl[2] = {0, 0};
+    for (size_t j = 0; j < nj; ++j)
+      for (int32_t k = A->kp0_begin[j]; k < A->kp0_begin[j + 1]; ++k)
+        if ((!A->use0 || A->use0[k]) && A->ray_valid0[k]) ++nl[A->job_mode[j]];
+    HIPCHK(hipSetDevice(c->device));
+    // device and pinned staging share one layout: uploaded [0, upEnd), read back [downBegin, downEnd),
+    // then what only the device holds
+    Arena M;
+    const size_t o_cam = M.reserve(8 * cam.size()), o_c0 = M.reserve(4 * nj), o_c1 = M.reserve(4 * nj),
+                 o_p0 = M.reserve(56 * nj), o_p1 = M.reserve(56 * nj), o_x0 = M.reserve(56 * nj), o_x1 = M.reserve(56 * nj),
+                 o_b1 = M.reserve(4 * (nj + 1)), o_j0 = M.reserve(4 * n0), o_j1 = M.reserve(4 * n1),
+                 o_list = M.reserve(4 * (nl[0] + nl[1])), o_s0 = M.reserve(8 * n0), o_d0 = M.reserve(48 * n0),
+                 o_r0 = M.reserve(24 * n0), o_xy1 = M.reserve(16 * n1), o_s1 = M.reserve(8 * n1), o_d1 = M.reserve(48 * n1),
+                 o_r1 = M.reserve(24 * n1), o_v1 = M.reserve(n1), o_u1 = M.reserve(n1);
+    const size_t upEnd = M.size;
+    const size_t o_m = M.reserve(4 * n0), downBegin = o_m, o_d = M.reserve(4 * n0), o_pt = M.reserve(32 * n0),
+                 o_q = M.reserve(8 * n0), o_i = M.reserve(n0);
+    const size_t downEnd = M.size;
+    const size_t o_geo = M.reserve(8 * kFrameGeoDoubles * nj), o_e0 = M.reserve(24 * n0), o_e1 = M.reserve(24 * n1),
+                 o_f1 = M.reserve(n1);
+    if (M.size > c->frameMatchScratchBytes) {
+      if (c->frameMatchScratch) HIPCHK(hipFree(c->frameMatchScratch));
+      c->frameMatchScratch = nullptr;
+      c->frameMatchScratchBytes = 0;
+      HIPCHK(hipMalloc(&c->frameMatchScratch, M.size));
+      c->frameMatchScratchBytes = M.size;
+    }
+    char* dev = static_cast<char*>(c->frameMatchScratch);
+    char* host = c->paramStage(downEnd);
+    auto put = [&](size_t off, const void* src, size_t bytes) {
+      if (bytes) std::memcpy(host + off, src, bytes);
+    };
+    put(o_cam, cam.data(), 8 * cam.size());
+    put(o_c0, A->job_camera0, 4 * nj);
+    put(o_c1, A->job_camera1, 4 * nj);
+    put(o_p0, A->job_pose0, 56 * nj);
+    put(o_p1, A->job_pose1, 56 * nj);
+    put(o_x0, A->job_extrinsics0, 56 * nj);
+    put(o_x1, A->job_extrinsics1, 56 * nj);
+    put(o_b1, A->kp1_begin, 4 * (nj + 1));
+    {  // the job of every keypoint; the participating side-0 keypoints of the mode-0 jobs, then the mode-1 jobs'
+      int32_t* job0 = reinterpret_cast<int32_t*>(host + o_j0);
+      int32_t* job1 = reinterpret_cast<int32_t*>(host + o_j1);
+      int32_t* list = reinterpret_cast<int32_t*>(host + o_list);
+      size_t at[2] = {0, nl[0]};
+      for (size_t j = 0; j < nj; ++j) {
+        for (int32_t k = A->kp0_begin[j]; k < A->kp0_begin[j + 1]; ++k) {
+          job0[k] = (int32_t)j;
+          if ((!A->use0 || A->use0[k]) && A->ray_valid0[k]) list[at[A->job_mode[j]]++] = k;
+        }
+        for (int32_t k = A->kp1_begin[j]; k < A->kp1_begin[j + 1]; ++k) job1[k] = (int32_t)j;
+      }
+    }
+    put(o_s0, A->size0, 8 * n0);
+    put(o_d0, A->descriptor0, 48 * n0);
+    put(o_r0, A->ray0, 24 * n0);
+    put(o_xy1, A->keypoint1, 16 * n1);
+    put(o_s1, A->size1, 8 * n1);
+    put(o_d1, A->descriptor1, 48 * n1);
+    put(o_r1, A->ray1, 24 * n1);
+    put(o_v1, A->ray_valid1, n1);
+    if (A->use1) put(o_u1, A->use1, n1);
+    HIPCHK(hipMemcpyAsync(dev, host, upEnd, hipMemcpyHostToDevice, c->stream));
+    FrameMatchDev D{};
+    D.n_jobs = A->n_jobs;
+    D.n_kp0 = (int32_t)n0;
+    D.n_kp1 = (int32_t)n1;
+    D.n_list0 = (int32_t)nl[0];
+    D.n_list1 = (int32_t)nl[1];
+    {  // d < best as the reference starts it: uint32_t(threshold) in mode 0, the double itself in mode 1
+      const double t = A->matching_threshold;
+      const double lim = 385.0;  // above every distance of 384 bits
+      D.best_init[0] = !(t > 0.0) ? 0 : (int32_t)std::floor(std::min(t, lim));
+      D.best_init[1] = !(t > 0.0) ? 0 : (int32_t)std::ceil(std::min(t, lim));
+    }
+    auto at = [&](size_t off) { return dev + off; };
+    D.cam = reinterpret_cast<const double*>(at(o_cam));
+    D.job_cam0 = reinterpret_cast<const int32_t*>(at(o_c0));
+    D.job_cam1 = reinterpret_cast<const int32_t*>(at(o_c1));
+    D.job_pose0 = reinterpret_cast<const double*>(at(o_p0));
+    D.job_pose1 = reinterpret_cast<const double*>(at(o_p1));
+    D.job_ext0 = reinterpret_cast<const double*>(at(o_x0));
+    D.job_ext1 = reinterpret_cast<const double*>(at(o_x1));
+    D.kp1_begin = reinterpret_cast<const int32_t*>(at(o_b1));
+    D.kp0_job = reinterpret_cast<const int32_t*>(at(o_j0));
+    D.kp1_job = reinterpret_cast<const int32_t*>(at(o_j1));
+    D.kp_list = reinterpret_cast<const int32_t*>(at(o_list));
+    D.size0 = reinterpret_cast<const double*>(at(o_s0));
+    D.desc0 = reinterpret_cast<const uint32_t*>(at(o_d0));
+    D.ray0 = reinterpret_cast<const double*>(at(o_r0));
+    D.xy1 = reinterpret_cast<const double*>(at(o_xy1));
+    D.size1 = reinterpret_cast<const double*>(at(o_s1));
+    D.desc1 = reinterpret_cast<const uint32_t*>(at(o_d1));
+    D.ray1 = reinterpret_cast<const double*>(at(o_r1));
+    D.valid1 = reinterpret_cast<const uint8_t*>(at(o_v1));
+    D.use1 = A->use1 ? reinterpret_cast<const uint8_t*>(at(o_u1)) : nullptr;
+    D.job_geo = reinterpret_cast<double*>(at(o_geo));
+    D.e0 = reinterpret_cast<double*>(at(o_e0));
+    D.e1 = reinterpret_cast<double*>(at(o_e1));
+    D.flag1 = reinterpret_cast<uint8_t*>(at(o_f1));
+    D.out_match = reinterpret_cast<int32_t*>(at(o_m));
+    D.out_dist = reinterpret_cast<int32_t*>(at(o_d));
+    D.out_point = reinterpret_cast<double*>(at(o_pt));
+    D.out_quality = reinterpret_cast<double*>(at(o_q));
+    D.out_init = reinterpret_cast<uint8_t*>(at(o_i));
+    launch_match_frames_prepare(D, c->stream);
+    HIPCHK(hipGetLastError());
+    launch_match_frames(D, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host + downBegin, dev + downBegin, downEnd - downBegin, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    auto get = [&](void* dst, size_t off, size_t bytes) {
+      if (dst && bytes) std::memcpy(dst, host + off, bytes);
+    };
+    get(R->match, o_m, 4 * n0);
+    get(R->distance, o_d, 4 * n0);
+    get(R->point, o_pt, 32 * n0);
+    get(R->quality, o_q, 8 * n0);
+    get(R->initialisable, o_i, n0);
     return (int)OKVISGPU_OK;
   });
 }

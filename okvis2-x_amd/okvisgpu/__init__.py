@@ -212,6 +212,21 @@ class MatchResult(C.Structure):
                 ("point", _dp), ("cand_n", _ip), ("cand_is3d", _up), ("cand_obs", _ip), ("cand_projection", _dp)]
 
 
+class FrameMatchBatch(C.Structure):
+    """okvisgpu_frame_match_batch: jobs matching the keypoints of one image against those of another."""
+    _fields_ = [("n_cameras", C.c_int32), ("cameras", C.POINTER(Camera)), ("matching_threshold", C.c_double),
+                ("n_jobs", C.c_int32), ("job_mode", _ip), ("job_camera0", _ip), ("job_camera1", _ip),
+                ("job_pose0", _dp), ("job_pose1", _dp), ("job_extrinsics0", _dp), ("job_extrinsics1", _dp),
+                ("kp0_begin", _ip), ("kp1_begin", _ip),
+                ("keypoint0", _dp), ("size0", _dp), ("descriptor0", _up), ("ray0", _dp), ("ray_valid0", _up), ("use0", _up),
+                ("keypoint1", _dp), ("size1", _dp), ("descriptor1", _up), ("ray1", _dp), ("ray_valid1", _up), ("use1", _up)]
+
+
+class FrameMatchResult(C.Structure):
+    """okvisgpu_frame_match_result: the caller-owned outputs of okvisgpu_match_frames (any may be NULL)."""
+    _fields_ = [("match", _ip), ("distance", _ip), ("point", _dp), ("initialisable", _up), ("quality", _dp)]
+
+
 class TwoPoseEdges(C.Structure):
     _fields_ = [("n_edges", C.c_int32), ("ref_pose", _dp), ("other_pose", _dp),
                 ("n_cameras", C.c_int32), ("cameras", C.POINTER(Camera)), ("extrinsics", _dp),
@@ -255,7 +270,7 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_eval_host", "okvisgpu_plan_window", "okvisgpu_loss_evaluate", "okvisgpu_plan_digest",
     "okvisgpu_launch_regime", "okvisgpu_update_landmarks", "okvisgpu_covisibilities", "okvisgpu_imu_propagate",
     "okvisgpu_twopose_extrinsics_compute", "okvisgpu_twopose_extrinsics_evaluate", "okvisgpu_gauss_newton_step",
-    "okvisgpu_match_to_map", "okvisgpu_plan_assembly",
+    "okvisgpu_match_to_map", "okvisgpu_plan_assembly", "okvisgpu_match_frames",
 ]
 N_PHASES = 15
 TWOPOSE_MAX_CAMERAS = 6
@@ -324,6 +339,7 @@ def lib():
         L.okvisgpu_imu_append.argtypes = [C.c_void_p, C.POINTER(ImuAppendBatch), _ip]
         L.okvisgpu_imu_propagate.argtypes = [C.c_void_p, C.POINTER(ImuPropagateBatch), _ip]
         L.okvisgpu_match_to_map.argtypes = [C.c_void_p, C.POINTER(MatchBatch), C.POINTER(MatchResult)]
+        L.okvisgpu_match_frames.argtypes = [C.c_void_p, C.POINTER(FrameMatchBatch), C.POINTER(FrameMatchResult)]
         L.okvisgpu_twopose_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _dp, _dp]
         L.okvisgpu_twopose_extrinsics_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _up, _dp,
                                                           _dp]
@@ -604,6 +620,34 @@ def match_batch(poses, cameras, extrinsics, landmarks, landmark_quality, obs_beg
     b.n_jobs = len(k["job_camera"])
     b.cameras = cams
     b.imu_use, b.loop_closure, b.matching_threshold = int(bool(imu_use)), int(bool(loop_closure)), matching_threshold
+    for name, a in k.items():
+        ptr = {np.dtype(np.float64): _dp, np.dtype(np.int32): _ip, np.dtype(np.uint8): _up}[a.dtype]
+        setattr(b, name, a.ctypes.data_as(ptr))
+    return b, (cams, k)
+
+
+def frame_match_batch(cameras, job_mode, job_camera0, job_camera1, job_pose0, job_pose1, job_extrinsics0,
+                      job_extrinsics1, kp0_begin, kp1_begin, keypoint0, size0, descriptor0, ray0, ray_valid0,
+                      keypoint1, size1, descriptor1, ray1, ray_valid1, use0=None, use1=None, matching_threshold=60.0):
+    """An okvisgpu_frame_match_batch over numpy arrays (copied to the struct's types where they differ):
+    (struct, arrays it points into). `cameras` is a sequence of Camera; the other arguments are the
+    arrays of the header's struct, `use0` / `use1` None = NULL (every keypoint)."""
+    f8 = lambda a, *shape: np.ascontiguousarray(a, dtype=np.float64).reshape(*shape)
+    i4 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    u1 = lambda a, *shape: np.ascontiguousarray(a, dtype=np.uint8).reshape(*shape)
+    cams = (Camera * max(1, len(cameras)))(*cameras)
+    k = {"job_mode": i4(job_mode), "job_camera0": i4(job_camera0), "job_camera1": i4(job_camera1),
+         "job_pose0": f8(job_pose0, -1, 7), "job_pose1": f8(job_pose1, -1, 7),
+         "job_extrinsics0": f8(job_extrinsics0, -1, 7), "job_extrinsics1": f8(job_extrinsics1, -1, 7),
+         "kp0_begin": i4(kp0_begin), "kp1_begin": i4(kp1_begin)}
+    for side, (kp, size, desc, ray, valid, use) in enumerate(((keypoint0, size0, descriptor0, ray0, ray_valid0, use0),
+                                                              (keypoint1, size1, descriptor1, ray1, ray_valid1, use1))):
+        k.update({f"keypoint{side}": f8(kp, -1, 2), f"size{side}": f8(size, -1), f"descriptor{side}": u1(desc, -1, 48),
+                  f"ray{side}": f8(ray, -1, 3), f"ray_valid{side}": u1(valid, -1)})
+        if use is not None:
+            k[f"use{side}"] = u1(use, -1)
+    b = FrameMatchBatch()
+    b.n_cameras, b.n_jobs, b.cameras, b.matching_threshold = len(cameras), len(k["job_mode"]), cams, matching_threshold
     for name, a in k.items():
         ptr = {np.dtype(np.float64): _dp, np.dtype(np.int32): _ip, np.dtype(np.uint8): _up}[a.dtype]
         setattr(b, name, a.ctypes.data_as(ptr))
@@ -901,6 +945,22 @@ class Context:
             setattr(r, k, a.ctypes.data_as({np.dtype(np.float64): _dp, np.dtype(np.int32): _ip,
                                             np.dtype(np.uint8): _up}[a.dtype]))
         self._check(lib().okvisgpu_match_to_map(self.h, C.byref(batch), C.byref(r)), "okvisgpu_match_to_map")
+        return out
+
+    def match_frames(self, batch: FrameMatchBatch, fill=None):
+        """okvisgpu_match_frames (the matching loops of Frontend::matchMotionStereo and ::matchStereo) for a
+        batch built by frame_match_batch(): dict of match, distance [n_kp0], point [n_kp0, 4],
+        initialisable [n_kp0] (uint8), quality [n_kp0]. `fill` (a dict of per-output values) pre-fills
+        the arrays the call writes into."""
+        nk = int(batch.kp0_begin[batch.n_jobs]) if batch.kp0_begin else 0
+        spec = {"match": ((nk,), np.int32), "distance": ((nk,), np.int32), "point": ((nk, 4), np.float64),
+                "initialisable": ((nk,), np.uint8), "quality": ((nk,), np.float64)}
+        out = {k: np.full(shape, (fill or {}).get(k, 0), dtype=dt) for k, (shape, dt) in spec.items()}
+        r = FrameMatchResult()
+        for k, a in out.items():
+            setattr(r, k, a.ctypes.data_as({np.dtype(np.float64): _dp, np.dtype(np.int32): _ip,
+                                            np.dtype(np.uint8): _up}[a.dtype]))
+        self._check(lib().okvisgpu_match_frames(self.h, C.byref(batch), C.byref(r)), "okvisgpu_match_frames")
         return out
 
     def twopose_compute(self, edges: "TwoPoseBatch"):
