@@ -731,6 +731,144 @@ typedef struct okvisgpu_frame_match_result {  /* caller-owned, any may be NULL; 
 int okvisgpu_match_frames(okvisgpu_ctx* ctx, const okvisgpu_frame_match_batch* batch,
                           okvisgpu_frame_match_result* result);
 
+/* ---------------------------------------------------------------- place verification: matching
+ * (An addition to ABI 6: a new entry point and two new structs; OKVISGPU_ABI_VERSION stays 6.)
+ * The descriptor matching of Frontend::verifyRecognisedPlace (okvis_frontend/src/Frontend.cpp:316-345,
+ * timer "2.04 loop closure descriptor matching") on the GPU for a batch of candidates. A job is one
+ * candidate: the landmarks of one old frame against the images of the new multiframe. Neither this
+ * call nor okvisgpu_place_refine depends on the outcome of an earlier candidate, so every candidate of
+ * a frame (:833, :877) can go into one batch and the host walks the results in candidate order.
+ *
+ * Images: n_images images of new frames, their descriptors stored image after image (kp_begin); jobs
+ * normally share the images of one new multiframe. job_image[j][im] is the image of camera im, or -1
+ * where that camera has no image. Landmarks: stored job after job (lm_begin), within a job in ascending
+ * LandmarkId, as `landmarks` iterates at :317; a landmark's descriptors (desc_begin) are those of the old
+ * frame's keypoints carrying it, in (camera, keypoint) order, as :276-313 pushes them. The filter of
+ * :278-303 (lmId != 0, initialised, landmark.norm() >= 1e-12, the CNN classes) is the caller's fold: only
+ * the surviving landmarks are passed.
+ *
+ * Per (landmark, camera) with K > 0 keypoints in the camera's image: distMin starts at
+ * matching_threshold truncated to an unsigned integer (:326); the walk goes over the landmark's
+ * descriptors in order and within a descriptor over k ascending; a candidate replaces the best iff its
+ * Hamming distance over the 48 bytes is strictly smaller (:331); there is a match iff distMin <
+ * matching_threshold, compared as doubles (:338). So the match is the first (descriptor, keypoint) in
+ * that order attaining the minimum distance, if that minimum is below the truncated threshold. (:338
+ * tests distMin itself: with a threshold that has a fractional part its start already passes, so a pair
+ * whose walk replaces nothing is reported as the reference reports it, keypoint kMin = 0 at the truncated
+ * threshold. okvis configures an integer, 60.) job_image = -1, K = 0 or a landmark without descriptors
+ * (which the reference cannot have) give -1 / -1. job_matches is the reference's
+ * ctr (:339), the number of (landmark, camera) matches of the job; the `ctr < minInliers` test (:349)
+ * needs nothing else. The maps of :340-342 (`matches`, keyed by keypoint so that a later landmark
+ * overwrites an earlier one on the same keypoint, and `points`) stay with the caller, as do the RANSAC
+ * (:353-388, opengv) and the float-precision distinctiveness test (:390-432).
+ *
+ * Independent of the problem set with okvisgpu_set_problems (needs none, leaves the device parameter
+ * sets alone); uses the context's device and stream and returns with the results in the caller's
+ * arrays. A job's result does not depend on the rest of the batch and is the same bits on every run.
+ * n_jobs = 0 is valid. OKVISGPU_ERR_INVALID_ARGUMENT, before anything is launched or written, for a
+ * NULL ctx, batch or result, a missing array, a negative count, a CSR array not starting at 0 or not
+ * monotone, an image index outside [-1, n_images), and between okvisgpu_solve_begin and _solve_end;
+ * okvisgpu_last_error names the offender. */
+typedef struct okvisgpu_place_match_batch {
+  double matching_threshold;        /* briskMatchingThreshold_, 60.0 in the reference              */
+  int32_t n_cameras;
+  /* --- images of new frames */
+  int32_t n_images;
+  const int32_t* kp_begin;          /* [n_images+1] CSR into descriptor                            */
+  const uint8_t* descriptor;        /* [n_kp][48]                                                  */
+  /* --- jobs (candidates) */
+  int32_t n_jobs;
+  const int32_t* job_image;         /* [n_jobs][n_cameras] image of camera im, -1 = none           */
+  const int32_t* lm_begin;          /* [n_jobs+1] CSR over the landmarks                           */
+  /* --- landmarks */
+  const int32_t* desc_begin;        /* [n_lm+1] CSR into old_descriptor                            */
+  const uint8_t* old_descriptor;    /* [n_desc][48]                                                */
+} okvisgpu_place_match_batch;
+
+typedef struct okvisgpu_place_match_result {  /* caller-owned, any may be NULL */
+  int32_t* match_keypoint;          /* [n_lm][n_cameras] keypoint index within the image, -1 = none */
+  int32_t* match_distance;          /* [n_lm][n_cameras] Hamming distance of the match, -1 = none  */
+  int32_t* job_matches;             /* [n_jobs] ctr                                                */
+} okvisgpu_place_match_result;
+int okvisgpu_place_match(okvisgpu_ctx* ctx, const okvisgpu_place_match_batch* batch,
+                         okvisgpu_place_match_result* result);
+
+/* ---------------------------------------------------------------- place verification: refinement
+ * (An addition to ABI 6: a new entry point and two new structs; OKVISGPU_ABI_VERSION stays 6.)
+ * The pose-only refinement of Frontend::verifyRecognisedPlace after its RANSAC and the evaluation that
+ * follows (Frontend.cpp:434-598, timer "2.06 loop closure pose refinement") on the GPU. A job is one
+ * candidate that survived the RANSAC: pose = T_Sold_Snew enters as the RANSAC model (:438) and leaves
+ * as the solve's result (:562); its observations are the inlier correspondences in correspondence order
+ * (:468), each with the landmark in the old frame's S coordinates (constant, :480; a landmark seen in
+ * two cameras is simply given twice). The extrinsics are the current frame's T_SC (:456), constant (:460)
+ * and shared by the batch, as is the loss: the reference uses {OKVISGPU_LOSS_CAUCHY, 0, 3.0, 0} (:447).
+ *
+ * The solve is ::ceres::Solve with the default Solver::Options but for max_num_iterations (:559):
+ * TRUST_REGION / LEVENBERG_MARQUARDT over one 6-dimensional PoseManifold block, Jacobi scaling,
+ * tolerances 1e-6 (function) / 1e-10 (gradient) / 1e-8 (parameter), radius 1e4 in [1e-32, 1e16],
+ * min_relative_decrease 1e-3, LM diagonal clamped to [1e-6, 1e32], at most 5 consecutive invalid steps,
+ * monotonic steps. Every residual is ReprojectionError::EvaluateWithMinimalJacobians(pose, obs_point,
+ * T_SC of obs_camera), exactly what okvisgpu_eval_reprojection evaluates, with the loss applied through
+ * Ceres' Corrector ("robust losses" above); cost = 1/2 sum rho(|r|^2). The trust-region loop is
+ * TrustRegionMinimizer's as okvisgpu_solve runs it (iteration 0 with the gradient test, step validity
+ * from the model cost change, the parameter and the function tolerance test before the acceptance test,
+ * the same counting rules); the strategy is LevenbergMarquardtStrategy: with J the Jacobi-scaled
+ * corrected Jacobian, diagonal = clamp(diag(J^T J), 1e-6, 1e32) (formed anew unless it is being reused),
+ * D^2 = diagonal / radius, step = -(J^T J + D^2)^-1 J^T r; a failed factorisation or a non-finite step
+ * is an invalid step. Accepted with step quality q: radius = min(1e16, radius / max(1/3, 1 - (2q -
+ * 1)^3)), the decrease factor goes back to 2, a new diagonal is formed; rejected or invalid: radius /=
+ * decrease factor, the decrease factor doubles, the diagonal is reused. Ceres solves the damped problem
+ * by dense QR, the device solves the 6x6 normal equations by an FP64 Cholesky factorisation (a
+ * rounding-level deviation). The pose written back is the lowest-cost accepted point.
+ *
+ * After the solve (:565-598), at the refined pose: per observation the weighted residual r without the
+ * loss and its 2x6 minimal pose Jacobian J; the observation is an outlier iff |r| > 3.0 (written so: a
+ * NaN counts as an inlier, as in the reference); inliers add J^T J to H, n_outliers counts the outliers.
+ * The two ratio tests of :593-598 stay with the caller.
+ *
+ * num_iterations, num_successful_steps (iteration 0 included), num_unsuccessful_steps and
+ * termination_type have the meaning of okvisgpu_summary's. A job without observations: pose untouched, H
+ * zero, 0 iterations, costs 0, OKVISGPU_CONVERGENCE. A job whose initial evaluation is not finite:
+ * OKVISGPU_FAILURE, 0 iterations, pose untouched (H and n_outliers are still evaluated there).
+ *
+ * Independent of the problem set with okvisgpu_set_problems; uses the context's device and stream and
+ * returns with the results in the caller's arrays. A job's result does not depend on the rest of the
+ * batch and is the same bits on every run. n_jobs = 0 is valid. OKVISGPU_ERR_INVALID_ARGUMENT, before
+ * anything is launched or written, for a NULL ctx, batch or result, a missing array, a negative count,
+ * obs_begin not starting at 0 or not monotone, a camera index out of range, an unknown distortion
+ * model, an unknown loss kind, a non-positive loss scale, and between okvisgpu_solve_begin and
+ * _solve_end; okvisgpu_last_error names the offender. */
+typedef struct okvisgpu_place_refine_batch {
+  /* --- the camera rig, shared by the batch */
+  int32_t n_cameras;
+  const okvisgpu_camera* cameras;   /* [n_cameras]                                                 */
+  const double* extrinsics;         /* [n_cameras][7] T_SC of the current frame (:456)             */
+  okvisgpu_loss loss;               /* the reference: {OKVISGPU_LOSS_CAUCHY, 0, 3.0, 0} (:447)     */
+  int32_t max_num_iterations;       /* realtime_max_iterations (:559)                              */
+  /* --- jobs (candidates that survived the RANSAC) */
+  int32_t n_jobs;
+  double* pose;                     /* [n_jobs][7] T_Sold_Snew, in: the RANSAC model, out: refined */
+  const int32_t* obs_begin;         /* [n_jobs+1] CSR over the inlier observations                 */
+  /* --- observations */
+  const int32_t* obs_camera;        /* [n_obs]                                                     */
+  const double* obs_keypoint;       /* [n_obs][2]                                                  */
+  const double* obs_sqrt_info;      /* [n_obs][4] row-major 2x2, (8 / size) I                      */
+  const double* obs_point;          /* [n_obs][4] the landmark in the old frame's S coordinates    */
+} okvisgpu_place_refine_batch;
+
+typedef struct okvisgpu_place_refine_result {  /* caller-owned, any may be NULL; all [n_jobs] */
+  double* H;                        /* [n_jobs][36] row-major sum of J^T J over the inliers        */
+  int32_t* n_outliers;              /* additionalOutliers (:587)                                   */
+  double* initial_cost;
+  double* final_cost;
+  int32_t* num_iterations;
+  int32_t* num_successful_steps;
+  int32_t* num_unsuccessful_steps;
+  int32_t* termination_type;        /* okvisgpu_termination                                        */
+} okvisgpu_place_refine_result;
+int okvisgpu_place_refine(okvisgpu_ctx* ctx, const okvisgpu_place_refine_batch* batch,
+                          okvisgpu_place_refine_result* result);
+
 /* ---------------------------------------------------------------- post-solve landmark pass
  * (An addition to ABI 6: a new entry point and a new struct; no existing struct or call changes, so
  * OKVISGPU_ABI_VERSION stays 6 and a caller built against the earlier header keeps working.)

@@ -480,4 +480,40 @@ struct FrameMatchDev {
   uint8_t* out_init;
 };
 
+// Frontend::verifyRecognisedPlace's descriptor matching for a batch of candidates
+// (okvisgpu_place_match_batch on device; kernels_place.hip).
+struct PlaceMatchDev {
+  int32_t n_lm, n_cam;
+  int32_t best_init;              // distMin's start: the threshold truncated, clamped to [0, 385]
+  int32_t start_matches;          // best_init < threshold as doubles (a threshold with a fractional part)
+  const int32_t* kp_begin;        // [n_images+1]
+  const uint32_t* desc;           // [n_kp][12]
+  const int32_t* job_image;       // [n_jobs][n_cam]
+  const int32_t* lm_job;          // [n_lm]
+  const int32_t* desc_begin;      // [n_lm+1]
+  const uint32_t* old_desc;       // [n_desc][12]
+  int32_t* out_kp;                // [n_lm][n_cam]
+  int32_t* out_dist;              // [n_lm][n_cam]
+};
+
+// Frontend::verifyRecognisedPlace's pose refinement for a batch of candidates
+// (okvisgpu_place_refine_batch on device; kernels_place.hip). Per job out_real holds initial cost,
+// final cost, H [36]; out_int iterations, successful steps, unsuccessful steps, termination, outliers.
+constexpr int kPlaceReal = 38, kPlaceInt = 5;
+struct PlaceRefineDev {
+  int32_t n_jobs, max_iter;
+  int32_t loss_kind;
+  double loss_a, loss_b;
+  const double* cam;              // [n_cam][kCamDoubles]
+  const double* extr;             // [n_cam][7]
+  const int32_t* obs_begin;       // [n_jobs+1]
+  const int32_t* obs_cam;         // [n_obs]
+  const double* obs_kp;           // [n_obs][2]
+  const double* obs_L;            // [n_obs][4]
+  const double* obs_pt;           // [n_obs][4]
+  double* pose;                   // [n_jobs][7] in / out
+  double* out_real;               // [n_jobs][kPlaceReal]
+  int32_t* out_int;               // [n_jobs][kPlaceInt]
+};
+
 }  // namespace okg

@@ -85,12 +85,6 @@ __global__ __launch_bounds__(64) void k_match_frames_prepare(const FrameMatchDev
   }
 }
 
-__device__ __forceinline__ int waveMinInt(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(64) void k_match_frames(const FrameMatchDev F, int first, int count) {
   if ((int)blockIdx.x >= count) return;

@@ -101,6 +101,12 @@ void launch_match(const MatchDev& M, hipStream_t s);
 void launch_match_frames_prepare(const FrameMatchDev& F, hipStream_t s);
 void launch_match_frames(const FrameMatchDev& F, hipStream_t s);
 
+// Frontend::verifyRecognisedPlace (kernels_place.hip). okvisgpu_place_match: one wavefront per (landmark,
+// camera), every element of both outputs written. okvisgpu_place_refine: one workgroup per job runs the
+// whole Levenberg-Marquardt solve and the evaluation after it; every element of the outputs written.
+void launch_place_match(const PlaceMatchDev& M, hipStream_t s);
+void launch_place_refine(const PlaceRefineDev& R, hipStream_t s);
+
 // post-solve landmark pass (kernels_landmarks.hip): ViGraph::updateLandmarks on parameter set 0 (run
 // launch_select_current first), one lane per landmark. Outputs in device order: quality [n_lm],
 // flags [n_lm] (kLmInitialised | kLmReset | kLmNotInFront), obs_err [n_obs]; dirs [n_obs][3] is

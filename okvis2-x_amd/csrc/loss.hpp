@@ -1,7 +1,8 @@
-// loss.hpp — robust losses on the host (okvisgpu.h "robust losses"): ::ceres::LossFunction::Evaluate
+// loss.hpp — robust losses (okvisgpu.h "robust losses"): ::ceres::LossFunction::Evaluate
 // of the Ceres loss family (ceres-solver >= 2.1 loss_function.cc, restated: CauchyLoss, TukeyLoss,
 // HuberLoss, SoftLOneLoss, ArctanLoss, TolerantLoss), rho[0..2] = rho(s), rho'(s), rho''(s). Used by
-// the planner's validation (plan.cpp) and by the host-evaluated factors' corrector (runtime.cpp).
+// the planner's validation (plan.cpp), by the host-evaluated factors' corrector (runtime.cpp) and, on
+// the device, by the place refinement's corrector (kernels_place.hip).
 #pragma once
 
 #include <algorithm>
@@ -9,6 +10,14 @@
 #include <cmath>
 
 #include "../../include/okvisgpu.h"
+
+// (plan.cpp is also compiled by a plain host compiler, without HIP)
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define OKG_LOSS_HD __host__ __device__ inline
+#else
+#define OKG_LOSS_HD inline
+#endif
 
 namespace okg {
 
@@ -22,7 +31,7 @@ inline bool lossValid(const okvisgpu_loss& L) {
   return false;
 }
 
-inline void lossRho(const okvisgpu_loss& L, double s, double* rho) {
+OKG_LOSS_HD void lossRho(const okvisgpu_loss& L, double s, double* rho) {
   const double a = L.a;
   switch (L.kind) {
     case OKVISGPU_LOSS_CAUCHY: {

@@ -1,6 +1,7 @@
 // match_geometry.hpp — the geometry the descriptor matchers share (kernels_match.hip: Frontend::matchToMap;
 // kernels_match_frames.hip: Frontend::matchMotionStereo / matchStereo): 3-vectors, Eigen's normalized(),
-// T_WS T_SC, the 48-byte Hamming distance and triangulateFast. Device-only, register-resident.
+// T_WS T_SC, the 48-byte Hamming distance, the wavefront minimum and triangulateFast (also kernels_place.hip:
+// Frontend::verifyRecognisedPlace). Device-only, register-resident.
 #pragma once
 
 #include "okvisgpu_math.hpp"
@@ -43,6 +44,13 @@ __device__ __forceinline__ int hamming48(const uint32_t a[12], gptr<uint32_t> b)
 #pragma unroll
   for (int i = 0; i < 12; ++i) d += __popc(a[i] ^ b[i]);
   return d;
+}
+
+// the minimum over the wavefront, in every lane
+__device__ __forceinline__ int waveMinInt(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
+  return v;
 }
 
 // triangulateFast (stereo_triangulation.cpp:30-112)

@@ -229,6 +229,10 @@ struct okvisgpu_ctx {
   // outputs || rays in W, flags, job transforms): likewise
   void* frameMatchScratch = nullptr;
   size_t frameMatchScratchBytes = 0;
+  // okvisgpu_place_match's and okvisgpu_place_refine's device arrays (inputs || outputs): likewise, one
+  // buffer for both calls
+  void* placeScratch = nullptr;
+  size_t placeScratchBytes = 0;
   // the assembly work items as records (HostBatch::asm_rec, DevProblem::asm_rec): likewise outside
   // the arena table, uploaded by build(), grown as needed
   void* asmRecBuf = nullptr;
@@ -296,6 +300,7 @@ struct okvisgpu_ctx {
     if (asmRecBuf) (void)hipFree(asmRecBuf);
     if (matchScratch) (void)hipFree(matchScratch);
     if (frameMatchScratch) (void)hipFree(frameMatchScratch);
+    if (placeScratch) (void)hipFree(placeScratch);
     for (hipEvent_t e : forkEv) (void)hipEventDestroy(e);
     for (hipStream_t q : side)
       if (q) (void)hipStreamDestroy(q);
@@ -2272,6 +2277,209 @@ int okvisgpu_match_frames(okvisgpu_ctx* c, const okvisgpu_frame_match_batch* A, 
     get(R->point, o_pt, 32 * n0);
     get(R->quality, o_q, 8 * n0);
     get(R->initialisable, o_i, n0);
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_place_match(okvisgpu_ctx* c, const okvisgpu_place_match_batch* A, okvisgpu_place_match_result* R) {
+  if (!c || !A || !R) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_match: bad arguments");
+  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_match: call after solve_end");
+  if (A->n_jobs < 0 || A->n_cameras < 0 || A->n_images < 0)
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_match: negative count");
+  if (A->n_jobs == 0) return OKVISGPU_OK;
+  return guarded(c, [&]() {
+    const std::string who = "place_match: ";
+    const size_t nj = (size_t)A->n_jobs, nc = (size_t)A->n_cameras, ni = (size_t)A->n_images;
+    if (!A->lm_begin || (nc && !A->job_image)) throw ArgError{who + "job arrays missing"};
+    if (ni && !A->kp_begin) throw ArgError{who + "kp_begin missing"};
+    if (ni && A->kp_begin[0] != 0) throw ArgError{who + "kp_begin must start at 0"};
+    for (size_t i = 0; i < ni; ++i)
+      if (A->kp_begin[i + 1] < A->kp_begin[i]) throw ArgError{who + "kp_begin not monotone at image " + std::to_string(i)};
+    const size_t nk = ni ? (size_t)A->kp_begin[ni] : 0;
+    if (nk && !A->descriptor) throw ArgError{who + "descriptor missing"};
+    if (A->lm_begin[0] != 0) throw ArgError{who + "lm_begin must start at 0"};
+    for (size_t j = 0; j < nj; ++j)
+      if (A->lm_begin[j + 1] < A->lm_begin[j]) throw ArgError{who + "lm_begin not monotone at job " + std::to_string(j)};
+    const size_t nl = (size_t)A->lm_begin[nj];
+    if (nl && !A->desc_begin) throw ArgError{who + "desc_begin missing"};
+    if (nl && A->desc_begin[0] != 0) throw ArgError{who + "desc_begin must start at 0"};
+    for (size_t l = 0; l < nl; ++l)
+      if (A->desc_begin[l + 1] < A->desc_begin[l])
+        throw ArgError{who + "desc_begin not monotone at landmark " + std::to_string(l)};
+    const size_t nd = nl ? (size_t)A->desc_begin[nl] : 0;
+    if (nd && !A->old_descriptor) throw ArgError{who + "old_descriptor missing"};
+    for (size_t i = 0; i < nj * nc; ++i)
+      if (A->job_image[i] < -1 || A->job_image[i] >= A->n_images)
+        throw ArgError{who + "job_image out of range at job " + std::to_string(i / nc)};
+    if (nl * nc > (size_t)0x7fffffff) throw ArgError{who + "too many (landmark, camera) pairs"};
+    const size_t no = nl * nc;
+    if (!no) {  // nothing to match: every job has ctr = 0
+      if (R->job_matches) std::fill(R->job_matches, R->job_matches + nj, 0);
+      return (int)OKVISGPU_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    // device and pinned staging share one layout: uploaded [0, upEnd), read back [downBegin, downEnd)
+    Arena M;
+    const size_t o_kb = M.reserve(4 * (ni + 1)), o_d = M.reserve(48 * nk), o_ji = M.reserve(4 * nj * nc),
+                 o_lj = M.reserve(4 * nl), o_db = M.reserve(4 * (nl + 1)), o_od = M.reserve(48 * nd);
+    const size_t upEnd = M.size;
+    const size_t o_k = M.reserve(4 * no), downBegin = o_k, o_dist = M.reserve(4 * no);
+    const size_t downEnd = M.size;
+    if (M.size > c->placeScratchBytes) {
+      if (c->placeScratch) HIPCHK(hipFree(c->placeScratch));
+      c->placeScratch = nullptr;
+      c->placeScratchBytes = 0;
+      HIPCHK(hipMalloc(&c->placeScratch, M.size));
+      c->placeScratchBytes = M.size;
+    }
+    char* dev = static_cast<char*>(c->placeScratch);
+    char* host = c->paramStage(downEnd);
+    auto put = [&](size_t off, const void* src, size_t bytes) {
+      if (bytes) std::memcpy(host + off, src, bytes);
+    };
+    if (ni) put(o_kb, A->kp_begin, 4 * (ni + 1));
+    else std::memset(host + o_kb, 0, 4);
+    put(o_d, A->descriptor, 48 * nk);
+    put(o_ji, A->job_image, 4 * nj * nc);
+    {  // the job of every landmark
+      int32_t* lj = reinterpret_cast<int32_t*>(host + o_lj);
+      for (size_t j = 0; j < nj; ++j)
+        for (int32_t l = A->lm_begin[j]; l < A->lm_begin[j + 1]; ++l) lj[l] = (int32_t)j;
+    }
+    put(o_db, A->desc_begin, 4 * (nl + 1));
+    put(o_od, A->old_descriptor, 48 * nd);
+    HIPCHK(hipMemcpyAsync(dev, host, upEnd, hipMemcpyHostToDevice, c->stream));
+    PlaceMatchDev D{};
+    D.n_lm = (int32_t)nl;
+    D.n_cam = (int32_t)nc;
+    {  // distMin's start: uint32_t(threshold), above no distance of 384 bits when clamped to 385
+      const double t = A->matching_threshold;
+      D.best_init = !(t > 0.0) ? 0 : (int32_t)std::floor(std::min(t, 385.0));
+      D.start_matches = (double)D.best_init < t && t <= 385.0;  // (:338 on a distMin nothing replaced)
+    }
+    D.kp_begin = reinterpret_cast<const int32_t*>(dev + o_kb);
+    D.desc = reinterpret_cast<const uint32_t*>(dev + o_d);
+    D.job_image = reinterpret_cast<const int32_t*>(dev + o_ji);
+    D.lm_job = reinterpret_cast<const int32_t*>(dev + o_lj);
+    D.desc_begin = reinterpret_cast<const int32_t*>(dev + o_db);
+    D.old_desc = reinterpret_cast<const uint32_t*>(dev + o_od);
+    D.out_kp = reinterpret_cast<int32_t*>(dev + o_k);
+    D.out_dist = reinterpret_cast<int32_t*>(dev + o_dist);
+    launch_place_match(D, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host + downBegin, dev + downBegin, downEnd - downBegin, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (R->match_keypoint) std::memcpy(R->match_keypoint, host + o_k, 4 * no);
+    if (R->match_distance) std::memcpy(R->match_distance, host + o_dist, 4 * no);
+    if (R->job_matches) {  // ctr: the job's (landmark, camera) pairs with a match
+      const int32_t* mk = reinterpret_cast<const int32_t*>(host + o_k);
+      for (size_t j = 0; j < nj; ++j) {
+        int32_t ctr = 0;
+        for (size_t i = (size_t)A->lm_begin[j] * nc; i < (size_t)A->lm_begin[j + 1] * nc; ++i) ctr += mk[i] >= 0;
+        R->job_matches[j] = ctr;
+      }
+    }
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_place_refine(okvisgpu_ctx* c, const okvisgpu_place_refine_batch* A, okvisgpu_place_refine_result* R) {
+  if (!c || !A || !R) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_refine: bad arguments");
+  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_refine: call after solve_end");
+  if (A->n_jobs < 0 || A->n_cameras < 0 || A->max_num_iterations < 0)
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_refine: negative count");
+  if (A->loss.kind < OKVISGPU_LOSS_NONE || A->loss.kind > OKVISGPU_LOSS_TOLERANT)
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_refine: unknown loss kind " + std::to_string(A->loss.kind));
+  if (!lossValid(A->loss)) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_refine: non-positive loss scale");
+  if (A->n_jobs == 0) return OKVISGPU_OK;
+  return guarded(c, [&]() {
+    const std::string who = "place_refine: ";
+    const size_t nj = (size_t)A->n_jobs, nc = (size_t)A->n_cameras;
+    if (!A->pose || !A->obs_begin) throw ArgError{who + "job arrays missing"};
+    if (A->obs_begin[0] != 0) throw ArgError{who + "obs_begin must start at 0"};
+    for (size_t j = 0; j < nj; ++j)
+      if (A->obs_begin[j + 1] < A->obs_begin[j]) throw ArgError{who + "obs_begin not monotone at job " + std::to_string(j)};
+    const size_t no = (size_t)A->obs_begin[nj];
+    if (no && (!A->obs_camera || !A->obs_keypoint || !A->obs_sqrt_info || !A->obs_point))
+      throw ArgError{who + "observation arrays missing"};
+    if (no && (!nc || !A->cameras || !A->extrinsics)) throw ArgError{who + "cameras missing"};
+    for (size_t o = 0; o < no; ++o)
+      if (A->obs_camera[o] < 0 || A->obs_camera[o] >= A->n_cameras)
+        throw ArgError{who + "obs_camera out of range at observation " + std::to_string(o)};
+    std::vector<double> cam((size_t)kCamDoubles * nc);
+    for (size_t k = 0; k < nc && A->cameras; ++k) {
+      const okvisgpu_camera& q = A->cameras[k];
+      if (q.distortion < 0 || q.distortion > 3) throw ArgError{who + "unknown distortion model of camera " + std::to_string(k)};
+      const double cv[kCamDoubles] = {(double)q.distortion, q.fu, q.fv, q.cu, q.cv, q.dist[0], q.dist[1], q.dist[2],
+                                      q.dist[3], q.dist[4], q.dist[5], q.dist[6], q.dist[7]};
+      std::memcpy(&cam[kCamDoubles * k], cv, sizeof(cv));
+    }
+    HIPCHK(hipSetDevice(c->device));
+    // device and pinned staging share one layout: uploaded [0, upEnd), read back [downBegin, downEnd);
+    // the poses are both
+    Arena M;
+    const size_t o_cam = M.reserve(8 * cam.size()), o_ex = M.reserve(56 * nc), o_ob = M.reserve(4 * (nj + 1)),
+                 o_oc = M.reserve(4 * no), o_kp = M.reserve(16 * no), o_L = M.reserve(32 * no), o_pt = M.reserve(32 * no);
+    const size_t o_pose = M.reserve(56 * nj), downBegin = o_pose;
+    const size_t upEnd = M.size;
+    const size_t o_real = M.reserve(8 * kPlaceReal * nj), o_int = M.reserve(4 * kPlaceInt * nj);
+    const size_t downEnd = M.size;
+    if (M.size > c->placeScratchBytes) {
+      if (c->placeScratch) HIPCHK(hipFree(c->placeScratch));
+      c->placeScratch = nullptr;
+      c->placeScratchBytes = 0;
+      HIPCHK(hipMalloc(&c->placeScratch, M.size));
+      c->placeScratchBytes = M.size;
+    }
+    char* dev = static_cast<char*>(c->placeScratch);
+    char* host = c->paramStage(downEnd);
+    auto put = [&](size_t off, const void* src, size_t bytes) {
+      if (bytes) std::memcpy(host + off, src, bytes);
+    };
+    put(o_cam, cam.data(), 8 * cam.size());
+    if (A->extrinsics) put(o_ex, A->extrinsics, 56 * nc);
+    put(o_ob, A->obs_begin, 4 * (nj + 1));
+    put(o_oc, A->obs_camera, 4 * no);
+    put(o_kp, A->obs_keypoint, 16 * no);
+    put(o_L, A->obs_sqrt_info, 32 * no);
+    put(o_pt, A->obs_point, 32 * no);
+    put(o_pose, A->pose, 56 * nj);
+    HIPCHK(hipMemcpyAsync(dev, host, upEnd, hipMemcpyHostToDevice, c->stream));
+    PlaceRefineDev D{};
+    D.n_jobs = A->n_jobs;
+    D.max_iter = A->max_num_iterations;
+    D.loss_kind = A->loss.kind;
+    D.loss_a = A->loss.a;
+    D.loss_b = A->loss.b;
+    D.cam = reinterpret_cast<const double*>(dev + o_cam);
+    D.extr = reinterpret_cast<const double*>(dev + o_ex);
+    D.obs_begin = reinterpret_cast<const int32_t*>(dev + o_ob);
+    D.obs_cam = reinterpret_cast<const int32_t*>(dev + o_oc);
+    D.obs_kp = reinterpret_cast<const double*>(dev + o_kp);
+    D.obs_L = reinterpret_cast<const double*>(dev + o_L);
+    D.obs_pt = reinterpret_cast<const double*>(dev + o_pt);
+    D.pose = reinterpret_cast<double*>(dev + o_pose);
+    D.out_real = reinterpret_cast<double*>(dev + o_real);
+    D.out_int = reinterpret_cast<int32_t*>(dev + o_int);
+    launch_place_refine(D, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host + downBegin, dev + downBegin, downEnd - downBegin, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const double* real = reinterpret_cast<const double*>(host + o_real);
+    const int32_t* in = reinterpret_cast<const int32_t*>(host + o_int);
+    for (size_t j = 0; j < nj; ++j) {
+      if (A->obs_begin[j + 1] > A->obs_begin[j]) std::memcpy(A->pose + 7 * j, host + o_pose + 56 * j, 56);
+      const double* r = real + kPlaceReal * j;
+      const int32_t* q = in + kPlaceInt * j;
+      if (R->initial_cost) R->initial_cost[j] = r[0];
+      if (R->final_cost) R->final_cost[j] = r[1];
+      if (R->H) std::memcpy(R->H + 36 * j, r + 2, 36 * sizeof(double));
+      if (R->num_iterations) R->num_iterations[j] = q[0];
+      if (R->num_successful_steps) R->num_successful_steps[j] = q[1];
+      if (R->num_unsuccessful_steps) R->num_unsuccessful_steps[j] = q[2];
+      if (R->termination_type) R->termination_type[j] = q[3];
+      if (R->n_outliers) R->n_outliers[j] = q[4];
+    }
     return (int)OKVISGPU_OK;
   });
 }

@@ -227,6 +227,31 @@ class FrameMatchResult(C.Structure):
     _fields_ = [("match", _ip), ("distance", _ip), ("point", _dp), ("initialisable", _up), ("quality", _dp)]
 
 
+class PlaceMatchBatch(C.Structure):
+    """okvisgpu_place_match_batch: candidates (old frames' landmarks) matched against new frames' images."""
+    _fields_ = [("matching_threshold", C.c_double), ("n_cameras", C.c_int32), ("n_images", C.c_int32),
+                ("kp_begin", _ip), ("descriptor", _up), ("n_jobs", C.c_int32), ("job_image", _ip), ("lm_begin", _ip),
+                ("desc_begin", _ip), ("old_descriptor", _up)]
+
+
+class PlaceMatchResult(C.Structure):
+    """okvisgpu_place_match_result: the caller-owned outputs of okvisgpu_place_match (any may be NULL)."""
+    _fields_ = [("match_keypoint", _ip), ("match_distance", _ip), ("job_matches", _ip)]
+
+
+class PlaceRefineBatch(C.Structure):
+    """okvisgpu_place_refine_batch: candidates whose relative pose is refined on their inlier observations."""
+    _fields_ = [("n_cameras", C.c_int32), ("cameras", C.POINTER(Camera)), ("extrinsics", _dp), ("loss", Loss),
+                ("max_num_iterations", C.c_int32), ("n_jobs", C.c_int32), ("pose", _dp), ("obs_begin", _ip),
+                ("obs_camera", _ip), ("obs_keypoint", _dp), ("obs_sqrt_info", _dp), ("obs_point", _dp)]
+
+
+class PlaceRefineResult(C.Structure):
+    """okvisgpu_place_refine_result: the caller-owned outputs of okvisgpu_place_refine (any may be NULL)."""
+    _fields_ = [("H", _dp), ("n_outliers", _ip), ("initial_cost", _dp), ("final_cost", _dp), ("num_iterations", _ip),
+                ("num_successful_steps", _ip), ("num_unsuccessful_steps", _ip), ("termination_type", _ip)]
+
+
 class TwoPoseEdges(C.Structure):
     _fields_ = [("n_edges", C.c_int32), ("ref_pose", _dp), ("other_pose", _dp),
                 ("n_cameras", C.c_int32), ("cameras", C.POINTER(Camera)), ("extrinsics", _dp),
@@ -270,7 +295,8 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_eval_host", "okvisgpu_plan_window", "okvisgpu_loss_evaluate", "okvisgpu_plan_digest",
     "okvisgpu_launch_regime", "okvisgpu_update_landmarks", "okvisgpu_covisibilities", "okvisgpu_imu_propagate",
     "okvisgpu_twopose_extrinsics_compute", "okvisgpu_twopose_extrinsics_evaluate", "okvisgpu_gauss_newton_step",
-    "okvisgpu_match_to_map", "okvisgpu_plan_assembly", "okvisgpu_match_frames",
+    "okvisgpu_match_to_map", "okvisgpu_plan_assembly", "okvisgpu_match_frames", "okvisgpu_place_match",
+    "okvisgpu_place_refine",
 ]
 N_PHASES = 15
 TWOPOSE_MAX_CAMERAS = 6
@@ -340,6 +366,8 @@ def lib():
         L.okvisgpu_imu_propagate.argtypes = [C.c_void_p, C.POINTER(ImuPropagateBatch), _ip]
         L.okvisgpu_match_to_map.argtypes = [C.c_void_p, C.POINTER(MatchBatch), C.POINTER(MatchResult)]
         L.okvisgpu_match_frames.argtypes = [C.c_void_p, C.POINTER(FrameMatchBatch), C.POINTER(FrameMatchResult)]
+        L.okvisgpu_place_match.argtypes = [C.c_void_p, C.POINTER(PlaceMatchBatch), C.POINTER(PlaceMatchResult)]
+        L.okvisgpu_place_refine.argtypes = [C.c_void_p, C.POINTER(PlaceRefineBatch), C.POINTER(PlaceRefineResult)]
         L.okvisgpu_twopose_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _dp, _dp]
         L.okvisgpu_twopose_extrinsics_compute.argtypes = [C.c_void_p, C.POINTER(TwoPoseEdges), _dp, _dp, _dp, _up, _dp,
                                                           _dp]
@@ -654,6 +682,49 @@ def frame_match_batch(cameras, job_mode, job_camera0, job_camera1, job_pose0, jo
     return b, (cams, k)
 
 
+def _set_arrays(b, arrays):
+    for name, a in arrays.items():
+        ptr = {np.dtype(np.float64): _dp, np.dtype(np.int32): _ip, np.dtype(np.uint8): _up}[a.dtype]
+        setattr(b, name, a.ctypes.data_as(ptr))
+
+
+def place_match_batch(n_cameras, kp_begin, descriptor, job_image, lm_begin, desc_begin, old_descriptor,
+                      matching_threshold=60.0):
+    """An okvisgpu_place_match_batch over numpy arrays (copied to the struct's types where they differ):
+    (struct, arrays it points into). The arguments are the arrays of the header's struct; `job_image` is
+    [n_jobs, n_cameras]."""
+    i4 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    u1 = lambda a: np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, 48)
+    k = {"kp_begin": i4(kp_begin), "descriptor": u1(descriptor), "job_image": i4(job_image), "lm_begin": i4(lm_begin),
+         "desc_begin": i4(desc_begin), "old_descriptor": u1(old_descriptor)}
+    b = PlaceMatchBatch()
+    b.matching_threshold, b.n_cameras = matching_threshold, int(n_cameras)
+    b.n_images, b.n_jobs = len(k["kp_begin"]) - 1, len(k["lm_begin"]) - 1
+    _set_arrays(b, k)
+    return b, k
+
+
+def place_refine_batch(cameras, extrinsics, pose, obs_begin, obs_camera, obs_keypoint, obs_sqrt_info, obs_point,
+                       loss=("cauchy", 3.0), max_num_iterations=10):
+    """An okvisgpu_place_refine_batch over numpy arrays (copied to the struct's types where they differ):
+    (struct, arrays it points into). `cameras` is a sequence of Camera; `pose` [n_jobs, 7] (float64,
+    C-contiguous) is referenced, not copied: the call refines it in place. `loss` is (kind name or id, a[, b])."""
+    f8 = lambda a, *shape: np.ascontiguousarray(a, dtype=np.float64).reshape(*shape)
+    i4 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    cams = (Camera * max(1, len(cameras)))(*cameras)
+    k = {"extrinsics": f8(extrinsics, -1, 7), "obs_begin": i4(obs_begin), "obs_camera": i4(obs_camera),
+         "obs_keypoint": f8(obs_keypoint, -1, 2), "obs_sqrt_info": f8(obs_sqrt_info, -1, 4),
+         "obs_point": f8(obs_point, -1, 4)}
+    n = len(k["obs_begin"]) - 1
+    assert pose.dtype == np.float64 and pose.flags["C_CONTIGUOUS"] and pose.shape == (n, 7)
+    b = PlaceRefineBatch()
+    b.n_cameras, b.cameras, b.n_jobs, b.max_num_iterations = len(cameras), cams, n, int(max_num_iterations)
+    b.loss = Loss(*loss_array([loss])[0].tolist())
+    b.pose = dptr(pose)
+    _set_arrays(b, k)
+    return b, (cams, k, pose)
+
+
 class TwoPoseBatch:
     """Owns the arrays of an okvisgpu_twopose_edges batch (TwoPoseStandardGraphError::compute inputs).
 
@@ -961,6 +1032,36 @@ class Context:
             setattr(r, k, a.ctypes.data_as({np.dtype(np.float64): _dp, np.dtype(np.int32): _ip,
                                             np.dtype(np.uint8): _up}[a.dtype]))
         self._check(lib().okvisgpu_match_frames(self.h, C.byref(batch), C.byref(r)), "okvisgpu_match_frames")
+        return out
+
+    def place_match(self, batch: PlaceMatchBatch, fill=None):
+        """okvisgpu_place_match (the descriptor matching of Frontend::verifyRecognisedPlace) for a batch built
+        by place_match_batch(): dict of match_keypoint, match_distance [n_lm, n_cameras], job_matches
+        [n_jobs]. `fill` (a dict of per-output values) pre-fills the arrays the call writes into."""
+        nj, nc = batch.n_jobs, batch.n_cameras
+        nl = int(batch.lm_begin[nj]) if batch.lm_begin else 0
+        spec = {"match_keypoint": (nl, nc), "match_distance": (nl, nc), "job_matches": (nj,)}
+        out = {k: np.full(shape, (fill or {}).get(k, 0), dtype=np.int32) for k, shape in spec.items()}
+        r = PlaceMatchResult()
+        _set_arrays(r, out)
+        self._check(lib().okvisgpu_place_match(self.h, C.byref(batch), C.byref(r)), "okvisgpu_place_match")
+        return out
+
+    def place_refine(self, batch: PlaceRefineBatch, fill=None):
+        """okvisgpu_place_refine (the pose refinement of Frontend::verifyRecognisedPlace and the evaluation
+        after it) for a batch built by place_refine_batch(): the batch's `pose` array is refined in place;
+        dict of H [n_jobs, 6, 6], n_outliers, initial_cost, final_cost, num_iterations,
+        num_successful_steps, num_unsuccessful_steps, termination_type [n_jobs]. `fill` (a dict of
+        per-output values) pre-fills the arrays the call writes into."""
+        n = batch.n_jobs
+        spec = {"H": ((n, 6, 6), np.float64), "n_outliers": ((n,), np.int32), "initial_cost": ((n,), np.float64),
+                "final_cost": ((n,), np.float64), "num_iterations": ((n,), np.int32),
+                "num_successful_steps": ((n,), np.int32), "num_unsuccessful_steps": ((n,), np.int32),
+                "termination_type": ((n,), np.int32)}
+        out = {k: np.full(shape, (fill or {}).get(k, 0), dtype=dt) for k, (shape, dt) in spec.items()}
+        r = PlaceRefineResult()
+        _set_arrays(r, out)
+        self._check(lib().okvisgpu_place_refine(self.h, C.byref(batch), C.byref(r)), "okvisgpu_place_refine")
         return out
 
     def twopose_compute(self, edges: "TwoPoseBatch"):
