@@ -5,48 +5,24 @@
 // window and the arena layout (plan.cpp), one HBM arena per context, upload, and the trust-region
 // iteration as a captured hipGraph that is replayed max_num_iterations times with every decision
 // taken on the device (kernels_control.hip). The host synchronises once per solve (plus once per
-// iteration only when a CeresIterationCallback-style time limit is requested).
-#include <hip/hip_runtime.h>
+// iteration only when a CeresIterationCallback-style time limit is requested). The call-scoped batch
+// entry points are in batch_calls.cpp; the context both files work on is declared in runtime.hpp.
+#include "runtime.hpp"
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <stdexcept>
-#include <string>
-#include <thread>
-#include <vector>
 
-#include "../../include/okvisgpu.h"
-#include "device_problem.hpp"
 #include "launch.hpp"
 #include "loss.hpp"
 #include "okvisgpu_math.hpp"
-#include "plan.hpp"
 
 using namespace okg;
 
 namespace {
-
-struct HipError {
-  std::string msg;
-  int code;
-};
-
-#define HIPCHK(x)                                                                             \
-  do {                                                                                        \
-    hipError_t e_ = (x);                                                                      \
-    if (e_ != hipSuccess)                                                                     \
-      throw HipError{std::string(#x) + ": " + hipGetErrorString(e_),                          \
-                     e_ == hipErrorOutOfMemory ? OKVISGPU_ERR_OUT_OF_MEMORY : OKVISGPU_ERR_DEVICE}; \
-  } while (0)
 
 double nowS() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -76,8 +52,8 @@ void forWindows(int n, F&& fn) {
   for (auto& x : th) x.join();
 }
 
-// Offsets of the arrays of a one-off device allocation (imu_append, twopose_compute; the batch's
-// arena is laid out by layoutArena, plan.hpp).
+// Offsets of okvisgpu_covisibilities' arrays in batchScratch (the batch's arena is laid out by
+// layoutArena, plan.hpp; a call-scoped batch by BatchLayout, batch_stage.hpp).
 struct Arena {
   size_t size = 0;
   size_t reserve(size_t bytes) {
@@ -89,986 +65,803 @@ struct Arena {
 
 }  // namespace
 
-// Persistent host worker threads of one context: the host-evaluated factors (ABI 5) are evaluated
-// at every point the solver evaluates, from the HIP callback thread of the iteration graph's host
-// node, so the workers are created once (grown on demand) instead of per evaluation. run(n, f)
-// calls f(0..n-1) on n workers and returns when all are done.
-class HostWorkers {
- public:
-  ~HostWorkers() {
-    {
-      std::lock_guard<std::mutex> l(m_);
-      stop_ = true;
-    }
-    wake_.notify_all();
-    for (auto& t : th_) t.join();
-  }
-  void run(int n, const std::function<void(int)>& f) {
-    while ((int)th_.size() < n) {
-      const int id = (int)th_.size();
-      th_.emplace_back([this, id]() { loop(id); });
-    }
-    std::unique_lock<std::mutex> l(m_);
-    job_ = &f;
-    njob_ = n;
-    pending_ = n;
-    ++gen_;
-    wake_.notify_all();
-    done_.wait(l, [&]() { return pending_ == 0; });
-    job_ = nullptr;
-  }
+void okvisgpu_ctx::decideRegime(int schedule) {
+  // the persistent kernels keep the window's rhs / y in dynamic LDS next to their static tiles
+  auto fits = [&](size_t staticLds) { return staticLds + sizeof(double) * (size_t)P.max_fpad <= ldsPerBlock; };
+  const char *ser = std::getenv("OKVISGPU_SERIAL_GRAPH"), *prep = std::getenv("OKVISGPU_LIN_PREP"),
+             *gi = std::getenv("OKVISGPU_GRAPH_ITERS");
+  const LaunchRegime r = launchRegime(P.n_win, cuCount, B.any_split, fits(persistentLds), fits(pipeLds), schedule,
+                                      ser && (ser[0] == '0' || ser[0] == '1') ? ser[0] - '0' : -1,
+                                      prep && prep[0] == '0' ? 0 : -1, gi && *gi ? std::max(0, std::atoi(gi)) : -1);
+  if (r.chol_schedule != regime.chol_schedule) dropGraph();
+  regime = r;
+  P.few = r.few; P.many = r.many; P.lin_prep = r.lin_prep; P.chol_schedule = r.chol_schedule;
+}
 
- private:
-  void loop(int id) {
-    uint64_t seen = 0;
-    std::unique_lock<std::mutex> l(m_);
-    for (;;) {
-      wake_.wait(l, [&]() { return stop_ || gen_ != seen; });
-      if (stop_) return;
-      seen = gen_;
-      if (id >= njob_) continue;
-      const std::function<void(int)>* f = job_;
-      l.unlock();
-      (*f)(id);
-      l.lock();
-      if (--pending_ == 0) done_.notify_all();
-    }
-  }
-  std::vector<std::thread> th_;
-  std::mutex m_;
-  std::condition_variable wake_, done_;
-  const std::function<void(int)>* job_ = nullptr;
-  int njob_ = 0, pending_ = 0;
-  uint64_t gen_ = 0;
-  bool stop_ = false;
-};
+// S is cleared by the build's arena memset; its padded diagonal (rows >= fdim) is set once per
+// build before the first factorisation (k_zero_S). The factorisation works in W and the assembly
+// overwrites its blocks, so S needs no clearing per iteration.
+void okvisgpu_ctx::ensureS(hipStream_t s) {
+  if (!sNeedsInit) return;
+  launch_zero_S(P, s);
+  sNeedsInit = false;
+}
 
-struct okvisgpu_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t side[3] = {nullptr, nullptr, nullptr};  // fork streams of the captured iteration graph
-  std::vector<hipEvent_t> forkEv;
-  size_t forkEvUsed = 0;  // events of forkEv taken by the capture in progress
-  std::string last_error;
-  HostBatch B;
-  std::vector<const okvisgpu_problem*> probs;
-  std::map<std::tuple<int, int, int>, int> constOverride;
-  void* hostStage = nullptr;  // pinned staging of the uploaded arrays (kept between set_problems)
-  size_t hostStageBytes = 0;
-  size_t arenaCap = 0;        // bytes allocated at `arena` (reused while a new batch fits)
-  bool structureDirty = false;
-  DevProblem P{};
-  void* arena = nullptr;
-  size_t arenaBytes = 0;
-  // The captured iteration, and graphIters = regime.graph_iters iterations captured as one graph as
-  // well (iterGraphK): solve_iterate runs n iterations as n / K launches of it and n mod K of the single one.
-  hipGraphExec_t iterGraph = nullptr, iterGraphK = nullptr;
-  int graphIters = 1;  // the K iterGraphK was captured with
-  int cuCount = 256;
-  size_t ldsPerBlock = 65536, persistentLds = 0, pipeLds = 0;  // device LDS; static LDS of the two Cholesky kernels
-  // The launch regime (plan.hpp), decided by setOptions() at solve_begin and, with default options,
-  // after a build; the launchers read its copy in P. The measurement switches are parsed here, once
-  // per decision: OKVISGPU_SERIAL_GRAPH=0|1, OKVISGPU_LIN_PREP=0, OKVISGPU_GRAPH_ITERS=<K>.
-  LaunchRegime regime;
-  void decideRegime(int schedule) {
-    // the persistent kernels keep the window's rhs / y in dynamic LDS next to their static tiles
-    auto fits = [&](size_t staticLds) { return staticLds + sizeof(double) * (size_t)P.max_fpad <= ldsPerBlock; };
-    const char *ser = std::getenv("OKVISGPU_SERIAL_GRAPH"), *prep = std::getenv("OKVISGPU_LIN_PREP"),
-               *gi = std::getenv("OKVISGPU_GRAPH_ITERS");
-    const LaunchRegime r = launchRegime(P.n_win, cuCount, B.any_split, fits(persistentLds), fits(pipeLds), schedule,
-                                        ser && (ser[0] == '0' || ser[0] == '1') ? ser[0] - '0' : -1,
-                                        prep && prep[0] == '0' ? 0 : -1, gi && *gi ? std::max(0, std::atoi(gi)) : -1);
-    if (r.chol_schedule != regime.chol_schedule) dropGraph();
-    regime = r;
-    P.few = r.few; P.many = r.many; P.lin_prep = r.lin_prep; P.chol_schedule = r.chol_schedule;
+void okvisgpu_ctx::fillSummaries(const std::vector<WinState>& st, okvisgpu_summary* sums) {
+  if (!sums) return;
+  const double t1 = nowS();
+  for (int w = 0; w < P.n_win; ++w) {
+    const WinState& s = st[w];
+    okvisgpu_summary& S = sums[w];
+    std::memset(&S, 0, sizeof(S));
+    S.initial_cost = s.initial_cost;
+    S.final_cost = std::min(s.min_cost, s.x_cost) + s.fixed_cost;
+    S.num_iterations = s.iteration;
+    S.num_successful_steps = s.num_succ + 1;  // Ceres counts iteration 0
+    S.num_unsuccessful_steps = s.num_unsucc;
+    S.termination_type = s.done ? s.termination : OKVISGPU_NO_CONVERGENCE;
+    S.total_time_s = t1 - solveT0;
+    S.final_radius = s.radius;
+    S.final_mu = s.mu;
+    S.preprocessor_time_s = tPre;
+    S.minimizer_time_s = tMin;
+    S.postprocessor_time_s = tPost;
+    S.linear_solver_time_s = S.residual_evaluation_time_s = S.jacobian_evaluation_time_s = S.step_time_s = -1.0;
+    if (phasesTimed) {  // phase ids: kPhaseNames
+      auto sum = [&](std::initializer_list<int> ids) {
+        double t = 0.0;
+        for (int i : ids) t += phaseMs[i];
+        return t * 1e-3;
+      };
+      S.linear_solver_time_s = sum({0, 1, 2, 3, 4, 5, 6, 7});
+      S.step_time_s = sum({8});
+      S.residual_evaluation_time_s = sum({9, 10, 11, 12});
+      S.jacobian_evaluation_time_s = sum({13, 14});
+    }
   }
-  // S is cleared by the build's arena memset; its padded diagonal (rows >= fdim) is set once per
-  // build before the first factorisation (k_zero_S). The factorisation works in W and the assembly
-  // overwrites its blocks, so S needs no clearing per iteration.
-  bool sNeedsInit = true;
-  void ensureS(hipStream_t s) {
-    if (!sNeedsInit) return;
-    launch_zero_S(P, s);
-    sNeedsInit = false;
-  }
-  bool haveProblem = false;
-  // split-solve state
-  bool inSolve = false;
-  okvisgpu_options opts{};
-  int replays = 0;
-  double solveT0 = 0.0;
-  // summary timings (okvisgpu_summary, ABI 6): wall clock of begin / iterations / write-back, and
-  // the iterations' device time per phase when the solve ran them eagerly (options.verbose)
-  double tPre = 0.0, tIterStart = 0.0, tMin = 0.0, tPost = 0.0;
-  bool phasesTimed = false;
-  double phaseMs[OKVISGPU_N_PHASES] = {};
-  // host-evaluated factors (ABI 5): pinned copies of host_in / host_out and per-factor failure
-  // flags of the last evaluation, written by hostEvaluate() on the HIP callback thread
-  double* hostIn = nullptr;
-  double* hostOut = nullptr;
-  int hostBufFactors = 0;
-  std::vector<uint8_t> hostFail;
-  HostWorkers hostWorkers;
-  // okvisgpu_update_landmarks' device outputs (quality | kept rays | observation errors | flags):
-  // owned by the context, outside the arena table, allocated on first use and grown as needed
-  void* lmScratch = nullptr;
-  size_t lmScratchBytes = 0;
-  // okvisgpu_covisibilities' device arrays (window records | work items | exclusion mask | bitset |
-  // counts | n_observed): likewise the context's own, outside the arena table, grown as needed
-  void* covisScratch = nullptr;
-  size_t covisScratchBytes = 0;
-  // okvisgpu_imu_propagate's device arrays (stamps | CSR | samples || poses | speed/biases || steps |
-  // covariance | Jacobian): likewise
-  void* propScratch = nullptr;
-  size_t propScratchBytes = 0;
-  // okvisgpu_match_to_map's device arrays (map | jobs | keypoints || per-slot scratch || candidate
-  // tables | per-keypoint outputs): likewise
-  void* matchScratch = nullptr;
-  size_t matchScratchBytes = 0;
-  // okvisgpu_match_frames' device arrays (cameras | jobs | lists | keypoints of both sides || per-keypoint
-  // outputs || rays in W, flags, job transforms): likewise
-  void* frameMatchScratch = nullptr;
-  size_t frameMatchScratchBytes = 0;
-  // okvisgpu_place_match's and okvisgpu_place_refine's device arrays (inputs || outputs): likewise, one
-  // buffer for both calls
-  void* placeScratch = nullptr;
-  size_t placeScratchBytes = 0;
-  // the assembly work items as records (HostBatch::asm_rec, DevProblem::asm_rec): likewise outside
-  // the arena table, uploaded by build(), grown as needed
-  void* asmRecBuf = nullptr;
-  size_t asmRecBytes = 0;
+}
 
-  void fillSummaries(const std::vector<WinState>& st, okvisgpu_summary* sums) {
-    if (!sums) return;
-    const double t1 = nowS();
-    for (int w = 0; w < P.n_win; ++w) {
-      const WinState& s = st[w];
-      okvisgpu_summary& S = sums[w];
-      std::memset(&S, 0, sizeof(S));
-      S.initial_cost = s.initial_cost;
-      S.final_cost = std::min(s.min_cost, s.x_cost) + s.fixed_cost;
-      S.num_iterations = s.iteration;
-      S.num_successful_steps = s.num_succ + 1;  // Ceres counts iteration 0
-      S.num_unsuccessful_steps = s.num_unsucc;
-      S.termination_type = s.done ? s.termination : OKVISGPU_NO_CONVERGENCE;
-      S.total_time_s = t1 - solveT0;
-      S.final_radius = s.radius;
-      S.final_mu = s.mu;
-      S.preprocessor_time_s = tPre;
-      S.minimizer_time_s = tMin;
-      S.postprocessor_time_s = tPost;
-      S.linear_solver_time_s = S.residual_evaluation_time_s = S.jacobian_evaluation_time_s = S.step_time_s = -1.0;
-      if (phasesTimed) {  // phase ids: kPhaseNames
-        auto sum = [&](std::initializer_list<int> ids) {
-          double t = 0.0;
-          for (int i : ids) t += phaseMs[i];
-          return t * 1e-3;
-        };
-        S.linear_solver_time_s = sum({0, 1, 2, 3, 4, 5, 6, 7});
-        S.step_time_s = sum({8});
-        S.residual_evaluation_time_s = sum({9, 10, 11, 12});
-        S.jacobian_evaluation_time_s = sum({13, 14});
-      }
+// end of a solve: iterations done (states were just read back), write-back, summaries
+void okvisgpu_ctx::finish(const std::vector<WinState>& st, okvisgpu_summary* sums) {
+  const double t = nowS();
+  tMin = t - tIterStart;
+  for (int w = 0; w < P.n_win; ++w)
+    if (st[w].dev_error) {
+      inSolve = false;
+      throw HipError{"window " + std::to_string(w) + ": the pipelined Cholesky's team wait reached its limit",
+                     OKVISGPU_ERR_DEVICE};
     }
-  }
+  downloadParams();
+  inSolve = false;
+  tPost = nowS() - t;
+  fillSummaries(st, sums);
+}
 
-  // end of a solve: iterations done (states were just read back), write-back, summaries
-  void finish(const std::vector<WinState>& st, okvisgpu_summary* sums) {
-    const double t = nowS();
-    tMin = t - tIterStart;
-    for (int w = 0; w < P.n_win; ++w)
-      if (st[w].dev_error) {
-        inSolve = false;
-        throw HipError{"window " + std::to_string(w) + ": the pipelined Cholesky's team wait reached its limit",
-                       OKVISGPU_ERR_DEVICE};
-      }
-    downloadParams();
-    inSolve = false;
-    tPost = nowS() - t;
-    fillSummaries(st, sums);
-  }
+okvisgpu_ctx::~okvisgpu_ctx() {
+  dropGraph();
+  if (arena) (void)hipFree(arena);
+  if (hostStage) (void)hipHostFree(hostStage);
+  if (hostIn) (void)hipHostFree(hostIn);
+  if (hostOut) (void)hipHostFree(hostOut);
+  for (hipEvent_t e : forkEv) (void)hipEventDestroy(e);
+  for (hipStream_t q : side)
+    if (q) (void)hipStreamDestroy(q);
+  if (stream) (void)hipStreamDestroy(stream);
+}
 
-  ~okvisgpu_ctx() {
-    dropGraph();
-    if (arena) (void)hipFree(arena);
-    if (hostStage) (void)hipHostFree(hostStage);
-    if (hostIn) (void)hipHostFree(hostIn);
-    if (hostOut) (void)hipHostFree(hostOut);
-    if (lmScratch) (void)hipFree(lmScratch);
-    if (covisScratch) (void)hipFree(covisScratch);
-    if (propScratch) (void)hipFree(propScratch);
-    if (asmRecBuf) (void)hipFree(asmRecBuf);
-    if (matchScratch) (void)hipFree(matchScratch);
-    if (frameMatchScratch) (void)hipFree(frameMatchScratch);
-    if (placeScratch) (void)hipFree(placeScratch);
-    for (hipEvent_t e : forkEv) (void)hipEventDestroy(e);
-    for (hipStream_t q : side)
-      if (q) (void)hipStreamDestroy(q);
-    if (stream) (void)hipStreamDestroy(stream);
+void okvisgpu_ctx::dropGraph() {
+  if (iterGraph) {
+    (void)hipGraphExecDestroy(iterGraph);
+    iterGraph = nullptr;
   }
+  if (iterGraphK) {
+    (void)hipGraphExecDestroy(iterGraphK);
+    iterGraphK = nullptr;
+  }
+  graphIters = 1;
+}
+// n iterations of the captured graph(s), in stream order
+void okvisgpu_ctx::launchIterations(int n) {
+  int k = 0;
+  if (iterGraphK)
+    for (; k + graphIters <= n; k += graphIters) HIPCHK(hipGraphLaunch(iterGraphK, stream));
+  for (; k < n; ++k) HIPCHK(hipGraphLaunch(iterGraph, stream));
+}
 
-  void dropGraph() {
-    if (iterGraph) {
-      (void)hipGraphExecDestroy(iterGraph);
-      iterGraph = nullptr;
-    }
-    if (iterGraphK) {
-      (void)hipGraphExecDestroy(iterGraphK);
-      iterGraphK = nullptr;
-    }
-    graphIters = 1;
-  }
-  // n iterations of the captured graph(s), in stream order
-  void launchIterations(int n) {
-    int k = 0;
-    if (iterGraphK)
-      for (; k + graphIters <= n; k += graphIters) HIPCHK(hipGraphLaunch(iterGraphK, stream));
-    for (; k < n; ++k) HIPCHK(hipGraphLaunch(iterGraph, stream));
-  }
+// ---- host-evaluated factors (SURVEY.md §8b fallback) ------------------------------------------
+// Every evaluation point (initial, each candidate) runs, in stream order: k_host_gather (the
+// blocks' values of the factors the eval mode selects) -> copy to pinned memory -> host node
+// (hostEvaluate: the caller's Evaluate on options.num_threads threads, manifold + loss applied
+// here) -> copy back -> k_host_scatter into the IMU-layout linearisation records. All of it is
+// graph-capturable (the host step is a host node of the captured iteration).
+void okvisgpu_ctx::ensureHostBuffers() {
+  hostFail.assign((size_t)P.n_host, 0);
+  if (P.n_host <= hostBufFactors) return;
+  if (hostIn) HIPCHK(hipHostFree(hostIn));
+  if (hostOut) HIPCHK(hipHostFree(hostOut));
+  hostIn = hostOut = nullptr;
+  hostBufFactors = 0;
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hostIn), sizeof(double) * kHostIn * P.n_host, hipHostMallocDefault));
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hostOut), sizeof(double) * kHostOut * P.n_host, hipHostMallocDefault));
+  hostBufFactors = P.n_host;
+}
 
-  // ---- host-evaluated factors (SURVEY.md §8b fallback) ------------------------------------------
-  // Every evaluation point (initial, each candidate) runs, in stream order: k_host_gather (the
-  // blocks' values of the factors the eval mode selects) -> copy to pinned memory -> host node
-  // (hostEvaluate: the caller's Evaluate on options.num_threads threads, manifold + loss applied
-  // here) -> copy back -> k_host_scatter into the IMU-layout linearisation records. All of it is
-  // graph-capturable (the host step is a host node of the captured iteration).
-  void ensureHostBuffers() {
-    hostFail.assign((size_t)P.n_host, 0);
-    if (P.n_host <= hostBufFactors) return;
-    if (hostIn) HIPCHK(hipHostFree(hostIn));
-    if (hostOut) HIPCHK(hipHostFree(hostOut));
-    hostIn = hostOut = nullptr;
-    hostBufFactors = 0;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hostIn), sizeof(double) * kHostIn * P.n_host, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hostOut), sizeof(double) * kHostOut * P.n_host, hipHostMallocDefault));
-    hostBufFactors = P.n_host;
-  }
+// PoseManifold plus Jacobian at x, 7x6 row-major (PoseLocalParameterization.cpp:56-68): the
+// minimal Jacobian of a pose-kind block is J_ambient * this, as Ceres applies a block's manifold.
+void okvisgpu_ctx::posePlusJacobian(const double* x, double* J) {
+  for (int i = 0; i < 42; ++i) J[i] = 0.0;
+  J[0 * 6 + 0] = J[1 * 6 + 1] = J[2 * 6 + 2] = 1.0;
+  const double qx = x[3], qy = x[4], qz = x[5], qw = x[6];
+  const double Q[4][3] = {{qw, qz, -qy}, {-qz, qw, qx}, {qy, -qx, qw}, {-qx, -qy, -qz}};  // oplus(q), cols 0..2
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 3; ++c) J[(3 + r) * 6 + 3 + c] = Q[r][c] * 0.5;
+}
 
-  // PoseManifold plus Jacobian at x, 7x6 row-major (PoseLocalParameterization.cpp:56-68): the
-  // minimal Jacobian of a pose-kind block is J_ambient * this, as Ceres applies a block's manifold.
-  static void posePlusJacobian(const double* x, double* J) {
-    for (int i = 0; i < 42; ++i) J[i] = 0.0;
-    J[0 * 6 + 0] = J[1 * 6 + 1] = J[2 * 6 + 2] = 1.0;
-    const double qx = x[3], qy = x[4], qz = x[5], qw = x[6];
-    const double Q[4][3] = {{qw, qz, -qy}, {-qz, qw, qx}, {qy, -qx, qw}, {-qx, -qy, -qz}};  // oplus(q), cols 0..2
-    for (int r = 0; r < 4; ++r)
-      for (int c = 0; c < 3; ++c) J[(3 + r) * 6 + 3 + c] = Q[r][c] * 0.5;
+// One host factor: Evaluate at the gathered point; r and the minimal Jacobian (IMU column
+// layout), corrected for the factor's loss (Ceres' Corrector, both branches) unless mode 3 (raw
+// evaluation), into its host_out record. Failure: cost +inf, r = J = 0.
+void okvisgpu_ctx::hostEvaluateOne(int h) {
+  const double* in = hostIn + (size_t)h * kHostIn;
+  double* out = hostOut + (size_t)h * kHostOut;
+  if (in[0] == 0.0) return;
+  const int mode = (int)in[1];
+  const HostBatch::HostFactor& F = B.hf[h];
+  const okvisgpu_problem* p = probs[F.win];
+  static const int at[4] = {8, 15, 24, 31}, col[4] = {0, 6, 15, 21};
+  const double* prm[4] = {nullptr, nullptr, nullptr, nullptr};
+  double amb[4][OKVISGPU_HOST_MAX_RESIDUALS * 9];
+  double* jac[4] = {nullptr, nullptr, nullptr, nullptr};
+  double r[OKVISGPU_HOST_MAX_RESIDUALS];
+  for (int k = 0; k < F.np; ++k) {
+    prm[k] = in + at[F.slot[k]];
+    jac[k] = amb[k];
+    std::memset(amb[k], 0, sizeof(amb[k]));
   }
-
-  // One host factor: Evaluate at the gathered point; r and the minimal Jacobian (IMU column
-  // layout), corrected for the factor's loss (Ceres' Corrector, both branches) unless mode 3 (raw
-  // evaluation), into its host_out record. Failure: cost +inf, r = J = 0.
-  void hostEvaluateOne(int h) {
-    const double* in = hostIn + (size_t)h * kHostIn;
-    double* out = hostOut + (size_t)h * kHostOut;
-    if (in[0] == 0.0) return;
-    const int mode = (int)in[1];
-    const HostBatch::HostFactor& F = B.hf[h];
-    const okvisgpu_problem* p = probs[F.win];
-    static const int at[4] = {8, 15, 24, 31}, col[4] = {0, 6, 15, 21};
-    const double* prm[4] = {nullptr, nullptr, nullptr, nullptr};
-    double amb[4][OKVISGPU_HOST_MAX_RESIDUALS * 9];
-    double* jac[4] = {nullptr, nullptr, nullptr, nullptr};
-    double r[OKVISGPU_HOST_MAX_RESIDUALS];
-    for (int k = 0; k < F.np; ++k) {
-      prm[k] = in + at[F.slot[k]];
-      jac[k] = amb[k];
-      std::memset(amb[k], 0, sizeof(amb[k]));
-    }
-    std::memset(r, 0, sizeof(r));
-    std::memset(out, 0, sizeof(double) * kHostOut);
-    int ok = 0;
-    try {
-      ok = p->host_evaluate(p->host_user, F.local, prm, r, jac);
-    } catch (...) {
-      ok = 0;
-    }
-    hostFail[h] = ok ? 0 : 1;
-    if (!ok) {
-      out[0] = HUGE_VAL;
-      return;
-    }
-    double sq = 0.0;
-    for (int i = 0; i < F.dim; ++i) sq += r[i] * r[i];
-    // minimal Jacobian (IMU column layout): ambient * PoseManifold plus Jacobian for pose-kind
-    // blocks, identity for speed/bias
-    double* J = out + 1 + 15;
-    for (int k = 0; k < F.np; ++k) {
-      const int q = F.slot[k];
-      if (q & 1) {  // speed/bias: identity manifold
-        for (int i = 0; i < F.dim; ++i)
-          for (int c = 0; c < 9; ++c) J[i * 30 + col[q] + c] = amb[k][i * 9 + c];
-      } else {
-        double Jp[42];
-        posePlusJacobian(prm[k], Jp);
-        for (int i = 0; i < F.dim; ++i)
-          for (int c = 0; c < 6; ++c) {
-            double s = 0.0;
-            for (int a = 0; a < 7; ++a) s += amb[k][i * 7 + a] * Jp[a * 6 + c];
-            J[i * 30 + col[q] + c] = s;
-          }
-      }
-    }
-    for (int i = 0; i < F.dim; ++i) out[1 + i] = r[i];
-    if (F.loss.kind == OKVISGPU_LOSS_NONE || mode == 3) {
-      out[0] = 0.5 * sq;
-      return;
-    }
-    // Ceres' Corrector (internal/ceres/corrector.cc; okvis restates it at TwoPoseGraphError.cpp:
-    // 292-337), applied to the minimal Jacobian as Ceres' ResidualBlock does after the manifold
-    double rho[3];
-    lossRho(F.loss, sq, rho);
-    out[0] = 0.5 * rho[0];
-    const double sqrtRho1 = std::sqrt(rho[1]);
-    double rScale = sqrtRho1, alphaSq = 0.0;
-    if (sq != 0.0 && rho[2] > 0.0) {  // second-order (Triggs) correction
-      const double D = 1.0 + 2.0 * sq * rho[2] / rho[1];
-      const double alpha = 1.0 - std::sqrt(D);
-      rScale = sqrtRho1 / (1.0 - alpha);
-      alphaSq = alpha / sq;
-    }
-    for (int k = 0; k < F.np; ++k) {
-      const int q = F.slot[k], nc = (q & 1) ? 9 : 6;
-      for (int c = 0; c < nc; ++c) {
-        double* Jc = J + col[q] + c;
-        if (alphaSq == 0.0) {
-          for (int i = 0; i < F.dim; ++i) Jc[i * 30] *= sqrtRho1;
-          continue;
+  std::memset(r, 0, sizeof(r));
+  std::memset(out, 0, sizeof(double) * kHostOut);
+  int ok = 0;
+  try {
+    ok = p->host_evaluate(p->host_user, F.local, prm, r, jac);
+  } catch (...) {
+    ok = 0;
+  }
+  hostFail[h] = ok ? 0 : 1;
+  if (!ok) {
+    out[0] = HUGE_VAL;
+    return;
+  }
+  double sq = 0.0;
+  for (int i = 0; i < F.dim; ++i) sq += r[i] * r[i];
+  // minimal Jacobian (IMU column layout): ambient * PoseManifold plus Jacobian for pose-kind
+  // blocks, identity for speed/bias
+  double* J = out + 1 + 15;
+  for (int k = 0; k < F.np; ++k) {
+    const int q = F.slot[k];
+    if (q & 1) {  // speed/bias: identity manifold
+      for (int i = 0; i < F.dim; ++i)
+        for (int c = 0; c < 9; ++c) J[i * 30 + col[q] + c] = amb[k][i * 9 + c];
+    } else {
+      double Jp[42];
+      posePlusJacobian(prm[k], Jp);
+      for (int i = 0; i < F.dim; ++i)
+        for (int c = 0; c < 6; ++c) {
+          double s = 0.0;
+          for (int a = 0; a < 7; ++a) s += amb[k][i * 7 + a] * Jp[a * 6 + c];
+          J[i * 30 + col[q] + c] = s;
         }
-        double rtj = 0.0;
-        for (int i = 0; i < F.dim; ++i) rtj += Jc[i * 30] * r[i];
-        for (int i = 0; i < F.dim; ++i) Jc[i * 30] = sqrtRho1 * (Jc[i * 30] - alphaSq * r[i] * rtj);
-      }
     }
-    for (int i = 0; i < F.dim; ++i) out[1 + i] = r[i] * rScale;
   }
-
-  void hostEvaluate() {
-    const int n = P.n_host;
-    const int nt = std::min(std::max(1, std::min(16, opts.num_threads)), n / 8);
-    if (nt <= 1) {
-      for (int h = 0; h < n; ++h) hostEvaluateOne(h);
-      return;
-    }
-    hostWorkers.run(nt, [this, n, nt](int t) {
-      for (int h = (int)((int64_t)n * t / nt); h < (int)((int64_t)n * (t + 1) / nt); ++h) hostEvaluateOne(h);
-    });
+  for (int i = 0; i < F.dim; ++i) out[1 + i] = r[i];
+  if (F.loss.kind == OKVISGPU_LOSS_NONE || mode == 3) {
+    out[0] = 0.5 * sq;
+    return;
   }
-  static void hostEvaluateCallback(void* self) { static_cast<okvisgpu_ctx*>(self)->hostEvaluate(); }
-
-  void evalHost(int mode, hipStream_t s) {
-    if (P.n_host == 0) return;
-    launch_host_gather(P, mode, s);
-    HIPCHK(hipMemcpyAsync(hostIn, P.host_in, sizeof(double) * kHostIn * P.n_host, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipLaunchHostFunc(s, hostEvaluateCallback, this));
-    HIPCHK(hipMemcpyAsync(P.host_out, hostOut, sizeof(double) * kHostOut * P.n_host, hipMemcpyHostToDevice, s));
-    launch_host_scatter(P, s);
+  // Ceres' Corrector (internal/ceres/corrector.cc; okvis restates it at TwoPoseGraphError.cpp:
+  // 292-337), applied to the minimal Jacobian as Ceres' ResidualBlock does after the manifold
+  double rho[3];
+  lossRho(F.loss, sq, rho);
+  out[0] = 0.5 * rho[0];
+  const double sqrtRho1 = std::sqrt(rho[1]);
+  double rScale = sqrtRho1, alphaSq = 0.0;
+  if (sq != 0.0 && rho[2] > 0.0) {  // second-order (Triggs) correction
+    const double D = 1.0 + 2.0 * sq * rho[2] / rho[1];
+    const double alpha = 1.0 - std::sqrt(D);
+    rScale = sqrtRho1 / (1.0 - alpha);
+    alphaSq = alpha / sq;
   }
-  // every residual of the batch at one evaluation point (mode: launch.hpp)
-  void evalAll(int mode, hipStream_t s) {
-    launch_eval(P, mode, s);
-    evalHost(mode, s);
-  }
-  // after the initial evaluation: a window whose host factor failed there ends with FAILURE
-  // (Ceres: "Residual and Jacobian evaluation failed" at iteration 0)
-  void failInitialHostEvaluations() {
-    if (P.n_host == 0) return;
-    HIPCHK(hipStreamSynchronize(stream));
-    std::vector<uint8_t> bad(P.n_win, 0);
-    bool any = false;
-    for (int h = 0; h < P.n_host; ++h)
-      if (hostFail[h]) any = bad[B.hf[h].win] = 1;
-    if (!any) return;
-    std::vector<WinState> st = readStates();
-    for (int w = 0; w < P.n_win; ++w)
-      if (bad[w]) {
-        st[w].done = 1;
-        st[w].termination = OKVISGPU_FAILURE;
-      }
-    HIPCHK(hipMemcpyAsync(P.st, st.data(), sizeof(WinState) * st.size(), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-  }
-
-  // (Re)build the device problem. Nothing of the previous batch survives a failure: the context
-  // holds no problem until a build completes (entry points then return OKVISGPU_ERR_NO_PROBLEM).
-  void build() {
-    haveProblem = false;
-    inSolve = false;
-    dropGraph();
-    const bool timing = std::getenv("OKVISGPU_BUILD_TIMING") != nullptr;  // development: host cost split
-    const auto tb0 = std::chrono::steady_clock::now();
-    {
-      HostBatch nb;
-      nb.opt = planOptions((int)probs.size(), cuCount);
-#ifdef OKG_ND_OVERRIDE
-      if (const char* e = std::getenv("OKVISGPU_ND")) nb.opt.nd = e[0] == '1';  // (development A/B builds only)
-#endif
-#ifdef OKG_LMG_OVERRIDE  // (development A/B builds only: OKVISGPU_LMG=visits,landmarks)
-      if (const char* e = std::getenv("OKVISGPU_LMG")) {
-        int v = 0, m = 0;
-        if (std::sscanf(e, "%d,%d", &v, &m) == 2 && v >= 1 && v <= kLmGroupVisits && m >= 1 && m <= kLmGroupMax) {
-          nb.opt.lmg_visits = v;
-          nb.opt.lmg_lms = m;
-        }
-      }
-#endif
-      analyse(probs, constOverride, nb);  // may throw: B is untouched until it succeeds
-      B = std::move(nb);
-    }
-    const auto tb1 = std::chrono::steady_clock::now();
-    const ArenaLayout L = layoutArena(B, cuCount, P);
-    // ---- allocate (reusing the arena while the batch fits) + upload: one contiguous host -> device
-    // copy of the uploaded region from the pinned staging buffer, one memset of the scratch region
-    const size_t upBytes = L.region_bytes[0], total = L.arenaBytes();
-    if (!arena || total > arenaCap) {
-      if (arena) {
-        HIPCHK(hipFree(arena));
-        arena = nullptr;
-        arenaCap = 0;
-      }
-      HIPCHK(hipMalloc(&arena, total));
-      arenaCap = total;
-    }
-    arenaBytes = total;
-    char* base = static_cast<char*>(arena);
-    char* stage = paramStage(upBytes);  // (synchronises: the previous upload is done)
-    const auto tb2 = std::chrono::steady_clock::now();
-    for (const ArenaBinding& b : L.table)
-      if (b.region == 0 && b.bytes) std::memcpy(stage + b.off, b.src, b.bytes);
-    const auto tb3 = std::chrono::steady_clock::now();
-    if (timing) {
-      auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-      std::fprintf(stderr, "okvisgpu build: analyse %.3f ms, layout+alloc %.3f ms, stage %.3f ms (%zu B)\n", ms(tb0, tb1),
-                   ms(tb1, tb2), ms(tb2, tb3), upBytes);
-    }
-    if (upBytes) HIPCHK(hipMemcpyAsync(base, stage, upBytes, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemsetAsync(base + L.scratchBase(), 0, L.region_bytes[1], stream));
-    sNeedsInit = true;
-    L.patch(base);
-    P.gL = P.lm_g;  // the landmark gradient is the accumulated J_l^T r
-    {  // the assembly records: the context's own buffer (not an arena-table entry)
-      const size_t need = std::max<size_t>(sizeof(AsmRec), B.asm_rec.size() * sizeof(AsmRec));
-      if (need > asmRecBytes) {
-        if (asmRecBuf) HIPCHK(hipFree(asmRecBuf));
-        asmRecBuf = nullptr;
-        asmRecBytes = 0;
-        HIPCHK(hipMalloc(&asmRecBuf, need));
-        asmRecBytes = need;
-      }
-      if (!B.asm_rec.empty())
-        HIPCHK(hipMemcpyAsync(asmRecBuf, B.asm_rec.data(), B.asm_rec.size() * sizeof(AsmRec), hipMemcpyHostToDevice, stream));
-      P.asm_rec = static_cast<const AsmRec*>(asmRecBuf);
-    }
-    HIPCHK(hipStreamSynchronize(stream));
-    decideRegime(0);  // (default options: the entry points that launch without a solve_begin)
-    uploadDescriptor();
-    ensureHostBuffers();
-    haveProblem = true;
-    structureDirty = false;
-  }
-
-  // Kernels read the descriptor through one pointer to device memory (a 1.3 KB by-value kernarg is
-  // re-fetched field by field on every dependent access).
-  void uploadDescriptor() {
-    HIPCHK(hipMemcpyAsync(const_cast<DevProblem*>(P.self), &P, sizeof(DevProblem), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-  }
-
-  void setOptions(const okvisgpu_options& o) {
-    DevOptions& d = P.opt;
-    d.max_num_iterations = o.max_num_iterations;
-    d.jacobi_scaling = o.jacobi_scaling;
-    d.max_num_consecutive_invalid_steps = o.max_num_consecutive_invalid_steps;
-    d.redo_propagation_always = o.redo_propagation_always;
-    d.function_tolerance = o.function_tolerance;
-    d.gradient_tolerance = o.gradient_tolerance;
-    d.parameter_tolerance = o.parameter_tolerance;
-    d.initial_radius = o.initial_trust_region_radius;
-    d.max_radius = o.max_trust_region_radius;
-    d.min_radius = o.min_trust_region_radius;
-    d.min_relative_decrease = o.min_relative_decrease;
-    d.min_lm_diagonal = o.min_lm_diagonal;
-    d.max_lm_diagonal = o.max_lm_diagonal;
-    decideRegime(o.cholesky_schedule);  // (drops the captured graph when the Cholesky schedule changes)
-    uploadDescriptor();
-  }
-
-  void resetStates(double mu) {
-    std::vector<WinState> s(P.n_win);
-    for (auto& x : s) {
-      std::memset(&x, 0, sizeof(x));
-      x.radius = P.opt.initial_radius;
-      x.mu = mu;
-      x.need_gn = 1;
-      x.z_mu = -1.0;
-      x.termination = OKVISGPU_NO_CONVERGENCE;
-    }
-    HIPCHK(hipMemcpyAsync(P.st, s.data(), sizeof(WinState) * s.size(), hipMemcpyHostToDevice, stream));
-  }
-
-  // Pinned staging for the parameter copies: the set_problems staging buffer (it holds both
-  // parameter sets and the IMU states, so it is large enough), grown if ever needed.
-  char* paramStage(size_t bytes) {
-    HIPCHK(hipStreamSynchronize(stream));  // no copy out of / into it is still in flight
-    if (bytes > hostStageBytes) {
-      if (hostStage) HIPCHK(hipHostFree(hostStage));
-      hostStage = nullptr;
-      hostStageBytes = 0;
-      HIPCHK(hipHostMalloc(&hostStage, bytes, hipHostMallocDefault));
-      hostStageBytes = bytes;
-    }
-    return static_cast<char*>(hostStage);
-  }
-
-  // Upload current host parameter values into both parameter sets (+ IMU state): the windows are
-  // packed into pinned memory in device order (host threads over windows), set 0 and the IMU
-  // states go up in one copy each, and set 1 is a device-side copy of set 0.
-  void uploadParams() {
-    const size_t np = 7 * (size_t)P.n_pose, ns = 9 * (size_t)P.n_sb, nl = 4 * (size_t)P.n_lm,
-                 ni = (size_t)P.n_imu * kImuState;
-    double* pose = reinterpret_cast<double*>(paramStage((np + ns + nl + ni) * 8));
-    double *sb = pose + np, *lm = sb + ns, *imu = lm + nl;
-    forWindows(B.n_win, [&](int w) {
-      const okvisgpu_problem* p = probs[w];
-      double* q = pose + 7 * (size_t)B.pose_base[w];
-      std::memcpy(q, p->poses, sizeof(double) * 7 * p->n_poses);
-      std::memcpy(q + 7 * (size_t)p->n_poses, p->extrinsics, sizeof(double) * 7 * p->n_cameras);
-      std::memcpy(sb + 9 * (size_t)B.sb_base[w], p->speed_biases, sizeof(double) * 9 * p->n_speed_biases);
-      double* l = lm + 4 * (size_t)B.lm_base[w];
-      const int* perm = &B.lm_perm[B.lm_base[w]];
-      for (int k = 0; k < p->n_landmarks; ++k) std::memcpy(l + 4 * (size_t)k, &p->landmarks[4 * (size_t)perm[k]], 32);
-      double* f = imu + (size_t)B.imu_base[w] * kImuState;
-      if (p->imu_state) std::memcpy(f, p->imu_state, sizeof(double) * kImuState * p->n_imu);
-      else std::memset(f, 0, sizeof(double) * kImuState * p->n_imu);
-    });
-    if (np) HIPCHK(hipMemcpyAsync(P.pose[0], pose, np * 8, hipMemcpyHostToDevice, stream));
-    if (ns) HIPCHK(hipMemcpyAsync(P.sb[0], sb, ns * 8, hipMemcpyHostToDevice, stream));
-    if (nl) HIPCHK(hipMemcpyAsync(P.lm[0], lm, nl * 8, hipMemcpyHostToDevice, stream));
-    if (ni) HIPCHK(hipMemcpyAsync(P.imu_state, imu, ni * 8, hipMemcpyHostToDevice, stream));
-    if (np) HIPCHK(hipMemcpyAsync(P.pose[1], P.pose[0], np * 8, hipMemcpyDeviceToDevice, stream));
-    if (ns) HIPCHK(hipMemcpyAsync(P.sb[1], P.sb[0], ns * 8, hipMemcpyDeviceToDevice, stream));
-    if (nl) HIPCHK(hipMemcpyAsync(P.lm[1], P.lm[0], nl * 8, hipMemcpyDeviceToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-  }
-
-  // Write device results back into the caller's arrays: k_select_current gathers every window's
-  // current parameter set into set 0 (WinState::xcur on the device), then one copy per array into
-  // pinned memory and a threaded scatter into the windows' arrays.
-  void downloadParams() {
-    const size_t np = 7 * (size_t)P.n_pose, ns = 9 * (size_t)P.n_sb, nl = 4 * (size_t)P.n_lm,
-                 ni = (size_t)P.n_imu * kImuState;
-    double* pose = reinterpret_cast<double*>(paramStage((np + ns + nl + ni) * 8));
-    double *sb = pose + np, *lm = sb + ns, *imu = lm + nl;
-    launch_select_current(P, stream);
-    HIPCHK(hipGetLastError());
-    if (np) HIPCHK(hipMemcpyAsync(pose, P.pose[0], np * 8, hipMemcpyDeviceToHost, stream));
-    if (ns) HIPCHK(hipMemcpyAsync(sb, P.sb[0], ns * 8, hipMemcpyDeviceToHost, stream));
-    if (nl) HIPCHK(hipMemcpyAsync(lm, P.lm[0], nl * 8, hipMemcpyDeviceToHost, stream));
-    if (ni) HIPCHK(hipMemcpyAsync(imu, P.imu_state, ni * 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    forWindows(B.n_win, [&](int w) {
-      const okvisgpu_problem* p = probs[w];
-      const double* q = pose + 7 * (size_t)B.pose_base[w];
-      std::memcpy(p->poses, q, sizeof(double) * 7 * p->n_poses);
-      if (B.win_ext_free[w])  // variable extrinsics are written back like every other block
-        std::memcpy(p->extrinsics, q + 7 * (size_t)p->n_poses, sizeof(double) * 7 * p->n_cameras);
-      std::memcpy(p->speed_biases, sb + 9 * (size_t)B.sb_base[w], sizeof(double) * 9 * p->n_speed_biases);
-      const double* l = lm + 4 * (size_t)B.lm_base[w];
-      const int* perm = &B.lm_perm[B.lm_base[w]];
-      for (int k = 0; k < p->n_landmarks; ++k) std::memcpy(&p->landmarks[4 * (size_t)perm[k]], l + 4 * (size_t)k, 32);
-      if (p->imu_state && p->n_imu)
-        std::memcpy(p->imu_state, imu + (size_t)B.imu_base[w] * kImuState, sizeof(double) * kImuState * p->n_imu);
-    });
-  }
-
-  // ViGraph::updateLandmarks on the current parameter values (okvisgpu_update_landmarks): every
-  // window's current set is gathered into set 0 as downloadParams does (before the first solve
-  // WinState is the build's zeroed scratch: xcur = 0, set 0 holds the uploaded values), one kernel
-  // over the batch's landmarks, one copy per output into pinned memory, and a threaded scatter into
-  // the caller's order (landmarks through lm_perm, observations through obs_orig). Of the caller's
-  // problem arrays only the re-placed landmarks are written.
-  void updateLandmarks(okvisgpu_landmark_update* U) {
-    for (int w = 0; w < B.n_win; ++w) {
-      U[w].n_initialised = U[w].n_reset = 0;
-      U[w].in_front = 1;
-      U[w].reserved = 0;
-    }
-    const size_t nl = (size_t)P.n_lm, no = (size_t)P.n_obs;
-    if (nl == 0) return;  // nothing to launch
-    bool wantErr = false;
-    for (int w = 0; w < B.n_win; ++w) wantErr = wantErr || U[w].obs_error != nullptr;
-    // device: quality [nl] | dirs [no][3] | err [no] | flags [nl]; host: quality [nl] | lm [nl][4] | err [no] | flags [nl]
-    const size_t need = 8 * (nl + 4 * std::max<size_t>(no, 1)) + nl;
-    if (need > lmScratchBytes) {
-      if (lmScratch) HIPCHK(hipFree(lmScratch));
-      lmScratch = nullptr;
-      lmScratchBytes = 0;
-      HIPCHK(hipMalloc(&lmScratch, need));
-      lmScratchBytes = need;
-    }
-    double* dQ = static_cast<double*>(lmScratch);
-    double *dDirs = dQ + nl, *dErr = dDirs + 3 * no;
-    uint8_t* dFlags = reinterpret_cast<uint8_t*>(dErr + std::max<size_t>(no, 1));
-    double* hQ = reinterpret_cast<double*>(paramStage(8 * (nl + 4 * nl + no) + nl));
-    double *hLm = hQ + nl, *hErr = hLm + 4 * nl;
-    uint8_t* hFlags = reinterpret_cast<uint8_t*>(hErr + no);
-    launch_select_current(P, stream);
-    launch_update_landmarks(P, dQ, dFlags, dErr, dDirs, stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hQ, dQ, nl * 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(hLm, P.lm[0], 4 * nl * 8, hipMemcpyDeviceToHost, stream));
-    if (wantErr && no) HIPCHK(hipMemcpyAsync(hErr, dErr, no * 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(hFlags, dFlags, nl, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    forWindows(B.n_win, [&](int w) {
-      const okvisgpu_problem* p = probs[w];
-      okvisgpu_landmark_update& u = U[w];
-      const size_t lb = (size_t)B.lm_base[w];
-      const int* perm = &B.lm_perm[lb];
-      int nInit = 0, nReset = 0, front = 1;
-      for (int k = 0; k < p->n_landmarks; ++k) {
-        const int l = perm[k];
-        const uint8_t f = hFlags[lb + k];
-        if (u.quality) u.quality[l] = hQ[lb + k];
-        if (u.initialised) u.initialised[l] = (f & kLmInitialised) ? 1 : 0;
-        if (u.reset) u.reset[l] = (f & kLmReset) ? 1 : 0;
-        nInit += (f & kLmInitialised) ? 1 : 0;
-        if (f & kLmNotInFront) front = 0;
-        if (f & kLmReset) {
-          ++nReset;
-          std::memcpy(&p->landmarks[4 * (size_t)l], hLm + 4 * (lb + k), 32);
-        }
-      }
-      u.n_initialised = nInit;
-      u.n_reset = nReset;
-      u.in_front = front;
-      if (u.obs_error) {
-        const size_t ob = (size_t)B.obs_base[w];
-        for (int k = 0; k < p->n_observations; ++k) u.obs_error[B.obs_orig[ob + k]] = hErr[ob + k];
-      }
-    });
-  }
-
-  // ViGraph::computeCovisibilities on the structure of the last set_problems
-  // (okvisgpu_covisibilities): a record per window that has states, landmarks and observations, the
-  // record of every 64-landmark word (k_covis_bits' work list), the work lists of the two count
-  // kernels (covisFitsLds picks a window's), the caller's exclusion masks
-  // permuted into internal landmark order; all of it packed into pinned memory and uploaded as one
-  // copy. k_covis_bits writes every word of the bitset and the count kernels every element of
-  // counts / n_observed, so nothing is cleared. One copy back per output, then a threaded scatter;
-  // the pair and visibility totals are taken on the host. Reads no parameter value and writes neither
-  // the caller's problem arrays nor the arena.
-  void covisibilities(okvisgpu_covisibility* V) {
-    const int nwin = B.n_win;
-    std::vector<CovisWin> recs;
-    std::vector<int> recOf((size_t)nwin, -1);
-    std::vector<int32_t> items0, items1, wordRec;  // wordRec: the record of each 64-landmark word
-    size_t lds0 = 0;
-    int64_t words = 0, bitsTot = 0, cntTot = 0, stateTot = 0;
-    bool anyMask = false;
-    for (int w = 0; w < nwin; ++w) {
-      const okvisgpu_problem* p = probs[w];
-      V[w].n_pairs = V[w].n_visible = V[w].any = V[w].path = 0;
-      if (p->n_poses <= 0 || p->n_landmarks <= 0 || p->n_observations <= 0) {  // all zeros, nothing to launch
-        const size_t S = (size_t)std::max(p->n_poses, 0);
-        if (V[w].counts) std::memset(V[w].counts, 0, 4 * S * S);
-        if (V[w].n_observed) std::memset(V[w].n_observed, 0, 4 * S);
-        if (V[w].visible) std::memset(V[w].visible, 0, S);
+  for (int k = 0; k < F.np; ++k) {
+    const int q = F.slot[k], nc = (q & 1) ? 9 : 6;
+    for (int c = 0; c < nc; ++c) {
+      double* Jc = J + col[q] + c;
+      if (alphaSq == 0.0) {
+        for (int i = 0; i < F.dim; ++i) Jc[i * 30] *= sqrtRho1;
         continue;
       }
-      CovisWin r{};
-      r.lm_begin = B.lm_base[w];
-      r.n_lm = p->n_landmarks;
-      r.pose_begin = B.pose_base[w];
-      r.n_state = p->n_poses;
-      r.word_begin = (int32_t)words;
-      r.n_words = (p->n_landmarks + 63) / 64;
-      r.state_off = (int32_t)stateTot;
-      r.bits_off = bitsTot;
-      r.counts_off = cntTot;
-      const int idx = (int)recs.size();
-      if (covisFitsLds(r.n_state, r.n_words)) {
-        items0.push_back(idx);
-        lds0 = std::max(lds0, covisLdsBytes(r.n_state, r.n_words));
-      } else {
-        V[w].path = 1;
-        const int T = (r.n_state + kCovisTile - 1) / kCovisTile;
-        for (int ti = 0; ti < T; ++ti)
-          for (int tj = 0; tj <= ti; ++tj) items1.insert(items1.end(), {idx, ti, tj});
-      }
-      wordRec.insert(wordRec.end(), (size_t)r.n_words, idx);
-      words += r.n_words;
-      stateTot += r.n_state;
-      bitsTot += (int64_t)r.n_state * r.n_words;
-      cntTot += (int64_t)r.n_state * r.n_state;
-      anyMask = anyMask || V[w].landmark_excluded != nullptr;
-      recOf[w] = idx;
-      recs.push_back(r);
+      double rtj = 0.0;
+      for (int i = 0; i < F.dim; ++i) rtj += Jc[i * 30] * r[i];
+      for (int i = 0; i < F.dim; ++i) Jc[i * 30] = sqrtRho1 * (Jc[i * 30] - alphaSq * r[i] * rtj);
     }
-    if (recs.empty()) return;
+  }
+  for (int i = 0; i < F.dim; ++i) out[1 + i] = r[i] * rScale;
+}
 
-    // device: uploaded part (records | word records | items0 | items1 | mask), then bits | counts | n_observed
-    const size_t nl = (size_t)P.n_lm;
-    Arena A;
-    const size_t oRec = A.reserve(sizeof(CovisWin) * recs.size()), oWr = A.reserve(4 * wordRec.size()),
-                 oI0 = A.reserve(4 * items0.size()), oI1 = A.reserve(4 * items1.size()), oEx = A.reserve(anyMask ? nl : 0);
-    const size_t upBytes = A.size;
-    const size_t oBits = A.reserve(8 * (size_t)bitsTot), oCnt = A.reserve(4 * (size_t)cntTot),
-                 oObs = A.reserve(4 * (size_t)stateTot);
-    if (A.size > covisScratchBytes) {
-      if (covisScratch) HIPCHK(hipFree(covisScratch));
-      covisScratch = nullptr;
-      covisScratchBytes = 0;
-      HIPCHK(hipMalloc(&covisScratch, A.size));
-      covisScratchBytes = A.size;
+void okvisgpu_ctx::hostEvaluate() {
+  const int n = P.n_host;
+  const int nt = std::min(std::max(1, std::min(16, opts.num_threads)), n / 8);
+  if (nt <= 1) {
+    for (int h = 0; h < n; ++h) hostEvaluateOne(h);
+    return;
+  }
+  hostWorkers.run(nt, [this, n, nt](int t) {
+    for (int h = (int)((int64_t)n * t / nt); h < (int)((int64_t)n * (t + 1) / nt); ++h) hostEvaluateOne(h);
+  });
+}
+
+void okvisgpu_ctx::evalHost(int mode, hipStream_t s) {
+  if (P.n_host == 0) return;
+  launch_host_gather(P, mode, s);
+  HIPCHK(hipMemcpyAsync(hostIn, P.host_in, sizeof(double) * kHostIn * P.n_host, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipLaunchHostFunc(s, hostEvaluateCallback, this));
+  HIPCHK(hipMemcpyAsync(P.host_out, hostOut, sizeof(double) * kHostOut * P.n_host, hipMemcpyHostToDevice, s));
+  launch_host_scatter(P, s);
+}
+// every residual of the batch at one evaluation point (mode: launch.hpp)
+void okvisgpu_ctx::evalAll(int mode, hipStream_t s) {
+  launch_eval(P, mode, s);
+  evalHost(mode, s);
+}
+// after the initial evaluation: a window whose host factor failed there ends with FAILURE
+// (Ceres: "Residual and Jacobian evaluation failed" at iteration 0)
+void okvisgpu_ctx::failInitialHostEvaluations() {
+  if (P.n_host == 0) return;
+  HIPCHK(hipStreamSynchronize(stream));
+  std::vector<uint8_t> bad(P.n_win, 0);
+  bool any = false;
+  for (int h = 0; h < P.n_host; ++h)
+    if (hostFail[h]) any = bad[B.hf[h].win] = 1;
+  if (!any) return;
+  std::vector<WinState> st = readStates();
+  for (int w = 0; w < P.n_win; ++w)
+    if (bad[w]) {
+      st[w].done = 1;
+      st[w].termination = OKVISGPU_FAILURE;
     }
-    char* dev = static_cast<char*>(covisScratch);
-    // pinned: the uploaded part as on the device, then counts | n_observed as they come back
-    const size_t hCntOff = (upBytes + 255) & ~size_t(255), hObsOff = hCntOff + 4 * (size_t)cntTot;
-    char* host = paramStage(hObsOff + 4 * (size_t)stateTot);
-    std::memcpy(host + oRec, recs.data(), sizeof(CovisWin) * recs.size());
-    std::memcpy(host + oWr, wordRec.data(), 4 * wordRec.size());
-    if (!items0.empty()) std::memcpy(host + oI0, items0.data(), 4 * items0.size());
-    if (!items1.empty()) std::memcpy(host + oI1, items1.data(), 4 * items1.size());
-    if (anyMask)
-      forWindows(nwin, [&](int w) {
-        const okvisgpu_problem* p = probs[w];
-        uint8_t* ex = reinterpret_cast<uint8_t*>(host + oEx) + (size_t)B.lm_base[w];
-        const uint8_t* in = V[w].landmark_excluded;
-        const int* perm = &B.lm_perm[B.lm_base[w]];
-        if (!in) std::memset(ex, 0, (size_t)std::max(p->n_landmarks, 0));
-        else
-          for (int k = 0; k < p->n_landmarks; ++k) ex[k] = in[perm[k]] ? 1 : 0;
-      });
-    HIPCHK(hipMemcpyAsync(dev, host, upBytes, hipMemcpyHostToDevice, stream));
-    const CovisWin* dRec = reinterpret_cast<const CovisWin*>(dev + oRec);
-    unsigned long long* dBits = reinterpret_cast<unsigned long long*>(dev + oBits);
-    int32_t *dCnt = reinterpret_cast<int32_t*>(dev + oCnt), *dObs = reinterpret_cast<int32_t*>(dev + oObs);
-    launch_covis_bits(P, dRec, (int)recs.size(), reinterpret_cast<const int32_t*>(dev + oWr), (int)words,
-                      anyMask ? reinterpret_cast<const uint8_t*>(dev + oEx) : nullptr, dBits, stream);
-    launch_covis_counts(dRec, reinterpret_cast<const int32_t*>(dev + oI0), (int)items0.size(), lds0,
-                        reinterpret_cast<const int32_t*>(dev + oI1), (int)(items1.size() / 3), dBits, dCnt, dObs, stream);
-    HIPCHK(hipGetLastError());
-    const int32_t* hCnt = reinterpret_cast<const int32_t*>(host + hCntOff);
-    const int32_t* hObs = reinterpret_cast<const int32_t*>(host + hObsOff);
-    HIPCHK(hipMemcpyAsync(host + hCntOff, dCnt, 4 * (size_t)cntTot, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(host + hObsOff, dObs, 4 * (size_t)stateTot, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+  HIPCHK(hipMemcpyAsync(P.st, st.data(), sizeof(WinState) * st.size(), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+}
+
+// (Re)build the device problem. Nothing of the previous batch survives a failure: the context
+// holds no problem until a build completes (entry points then return OKVISGPU_ERR_NO_PROBLEM).
+void okvisgpu_ctx::build() {
+  haveProblem = false;
+  inSolve = false;
+  dropGraph();
+  const bool timing = std::getenv("OKVISGPU_BUILD_TIMING") != nullptr;  // development: host cost split
+  const auto tb0 = std::chrono::steady_clock::now();
+  {
+    HostBatch nb;
+    nb.opt = planOptions((int)probs.size(), cuCount);
+#ifdef OKG_ND_OVERRIDE
+    if (const char* e = std::getenv("OKVISGPU_ND")) nb.opt.nd = e[0] == '1';  // (development A/B builds only)
+#endif
+#ifdef OKG_LMG_OVERRIDE  // (development A/B builds only: OKVISGPU_LMG=visits,landmarks)
+    if (const char* e = std::getenv("OKVISGPU_LMG")) {
+      int v = 0, m = 0;
+      if (std::sscanf(e, "%d,%d", &v, &m) == 2 && v >= 1 && v <= kLmGroupVisits && m >= 1 && m <= kLmGroupMax) {
+        nb.opt.lmg_visits = v;
+        nb.opt.lmg_lms = m;
+      }
+    }
+#endif
+    analyse(probs, constOverride, nb);  // may throw: B is untouched until it succeeds
+    B = std::move(nb);
+  }
+  const auto tb1 = std::chrono::steady_clock::now();
+  const ArenaLayout L = layoutArena(B, cuCount, P);
+  // ---- allocate (reusing the arena while the batch fits) + upload: one contiguous host -> device
+  // copy of the uploaded region from the pinned staging buffer, one memset of the scratch region
+  const size_t upBytes = L.region_bytes[0], total = L.arenaBytes();
+  if (!arena || total > arenaCap) {
+    if (arena) {
+      HIPCHK(hipFree(arena));
+      arena = nullptr;
+      arenaCap = 0;
+    }
+    HIPCHK(hipMalloc(&arena, total));
+    arenaCap = total;
+  }
+  arenaBytes = total;
+  char* base = static_cast<char*>(arena);
+  char* stage = paramStage(upBytes);  // (synchronises: the previous upload is done)
+  const auto tb2 = std::chrono::steady_clock::now();
+  for (const ArenaBinding& b : L.table)
+    if (b.region == 0 && b.bytes) std::memcpy(stage + b.off, b.src, b.bytes);
+  const auto tb3 = std::chrono::steady_clock::now();
+  if (timing) {
+    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    std::fprintf(stderr, "okvisgpu build: analyse %.3f ms, layout+alloc %.3f ms, stage %.3f ms (%zu B)\n", ms(tb0, tb1),
+                 ms(tb1, tb2), ms(tb2, tb3), upBytes);
+  }
+  if (upBytes) HIPCHK(hipMemcpyAsync(base, stage, upBytes, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemsetAsync(base + L.scratchBase(), 0, L.region_bytes[1], stream));
+  sNeedsInit = true;
+  L.patch(base);
+  P.gL = P.lm_g;  // the landmark gradient is the accumulated J_l^T r
+  {  // the assembly records: the context's own buffer (not an arena-table entry)
+    const size_t need = std::max<size_t>(sizeof(AsmRec), B.asm_rec.size() * sizeof(AsmRec));
+    void* rec = asmRecBuf.need(need);
+    if (!B.asm_rec.empty())
+      HIPCHK(hipMemcpyAsync(rec, B.asm_rec.data(), B.asm_rec.size() * sizeof(AsmRec), hipMemcpyHostToDevice, stream));
+    P.asm_rec = static_cast<const AsmRec*>(rec);
+  }
+  HIPCHK(hipStreamSynchronize(stream));
+  decideRegime(0);  // (default options: the entry points that launch without a solve_begin)
+  uploadDescriptor();
+  ensureHostBuffers();
+  haveProblem = true;
+  structureDirty = false;
+}
+
+// Kernels read the descriptor through one pointer to device memory (a 1.3 KB by-value kernarg is
+// re-fetched field by field on every dependent access).
+void okvisgpu_ctx::uploadDescriptor() {
+  HIPCHK(hipMemcpyAsync(const_cast<DevProblem*>(P.self), &P, sizeof(DevProblem), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+}
+
+void okvisgpu_ctx::setOptions(const okvisgpu_options& o) {
+  DevOptions& d = P.opt;
+  d.max_num_iterations = o.max_num_iterations;
+  d.jacobi_scaling = o.jacobi_scaling;
+  d.max_num_consecutive_invalid_steps = o.max_num_consecutive_invalid_steps;
+  d.redo_propagation_always = o.redo_propagation_always;
+  d.function_tolerance = o.function_tolerance;
+  d.gradient_tolerance = o.gradient_tolerance;
+  d.parameter_tolerance = o.parameter_tolerance;
+  d.initial_radius = o.initial_trust_region_radius;
+  d.max_radius = o.max_trust_region_radius;
+  d.min_radius = o.min_trust_region_radius;
+  d.min_relative_decrease = o.min_relative_decrease;
+  d.min_lm_diagonal = o.min_lm_diagonal;
+  d.max_lm_diagonal = o.max_lm_diagonal;
+  decideRegime(o.cholesky_schedule);  // (drops the captured graph when the Cholesky schedule changes)
+  uploadDescriptor();
+}
+
+void okvisgpu_ctx::resetStates(double mu) {
+  std::vector<WinState> s(P.n_win);
+  for (auto& x : s) {
+    std::memset(&x, 0, sizeof(x));
+    x.radius = P.opt.initial_radius;
+    x.mu = mu;
+    x.need_gn = 1;
+    x.z_mu = -1.0;
+    x.termination = OKVISGPU_NO_CONVERGENCE;
+  }
+  HIPCHK(hipMemcpyAsync(P.st, s.data(), sizeof(WinState) * s.size(), hipMemcpyHostToDevice, stream));
+}
+
+// Pinned staging for the parameter copies: the set_problems staging buffer (it holds both
+// parameter sets and the IMU states, so it is large enough), grown if ever needed.
+char* okvisgpu_ctx::paramStage(size_t bytes) {
+  HIPCHK(hipStreamSynchronize(stream));  // no copy out of / into it is still in flight
+  if (bytes > hostStageBytes) {
+    if (hostStage) HIPCHK(hipHostFree(hostStage));
+    hostStage = nullptr;
+    hostStageBytes = 0;
+    HIPCHK(hipHostMalloc(&hostStage, bytes, hipHostMallocDefault));
+    hostStageBytes = bytes;
+  }
+  return static_cast<char*>(hostStage);
+}
+
+// Upload current host parameter values into both parameter sets (+ IMU state): the windows are
+// packed into pinned memory in device order (host threads over windows), set 0 and the IMU
+// states go up in one copy each, and set 1 is a device-side copy of set 0.
+void okvisgpu_ctx::uploadParams() {
+  const size_t np = 7 * (size_t)P.n_pose, ns = 9 * (size_t)P.n_sb, nl = 4 * (size_t)P.n_lm,
+               ni = (size_t)P.n_imu * kImuState;
+  double* pose = reinterpret_cast<double*>(paramStage((np + ns + nl + ni) * 8));
+  double *sb = pose + np, *lm = sb + ns, *imu = lm + nl;
+  forWindows(B.n_win, [&](int w) {
+    const okvisgpu_problem* p = probs[w];
+    double* q = pose + 7 * (size_t)B.pose_base[w];
+    std::memcpy(q, p->poses, sizeof(double) * 7 * p->n_poses);
+    std::memcpy(q + 7 * (size_t)p->n_poses, p->extrinsics, sizeof(double) * 7 * p->n_cameras);
+    std::memcpy(sb + 9 * (size_t)B.sb_base[w], p->speed_biases, sizeof(double) * 9 * p->n_speed_biases);
+    double* l = lm + 4 * (size_t)B.lm_base[w];
+    const int* perm = &B.lm_perm[B.lm_base[w]];
+    for (int k = 0; k < p->n_landmarks; ++k) std::memcpy(l + 4 * (size_t)k, &p->landmarks[4 * (size_t)perm[k]], 32);
+    double* f = imu + (size_t)B.imu_base[w] * kImuState;
+    if (p->imu_state) std::memcpy(f, p->imu_state, sizeof(double) * kImuState * p->n_imu);
+    else std::memset(f, 0, sizeof(double) * kImuState * p->n_imu);
+  });
+  if (np) HIPCHK(hipMemcpyAsync(P.pose[0], pose, np * 8, hipMemcpyHostToDevice, stream));
+  if (ns) HIPCHK(hipMemcpyAsync(P.sb[0], sb, ns * 8, hipMemcpyHostToDevice, stream));
+  if (nl) HIPCHK(hipMemcpyAsync(P.lm[0], lm, nl * 8, hipMemcpyHostToDevice, stream));
+  if (ni) HIPCHK(hipMemcpyAsync(P.imu_state, imu, ni * 8, hipMemcpyHostToDevice, stream));
+  if (np) HIPCHK(hipMemcpyAsync(P.pose[1], P.pose[0], np * 8, hipMemcpyDeviceToDevice, stream));
+  if (ns) HIPCHK(hipMemcpyAsync(P.sb[1], P.sb[0], ns * 8, hipMemcpyDeviceToDevice, stream));
+  if (nl) HIPCHK(hipMemcpyAsync(P.lm[1], P.lm[0], nl * 8, hipMemcpyDeviceToDevice, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+}
+
+// Write device results back into the caller's arrays: k_select_current gathers every window's
+// current parameter set into set 0 (WinState::xcur on the device), then one copy per array into
+// pinned memory and a threaded scatter into the windows' arrays.
+void okvisgpu_ctx::downloadParams() {
+  const size_t np = 7 * (size_t)P.n_pose, ns = 9 * (size_t)P.n_sb, nl = 4 * (size_t)P.n_lm,
+               ni = (size_t)P.n_imu * kImuState;
+  double* pose = reinterpret_cast<double*>(paramStage((np + ns + nl + ni) * 8));
+  double *sb = pose + np, *lm = sb + ns, *imu = lm + nl;
+  launch_select_current(P, stream);
+  HIPCHK(hipGetLastError());
+  if (np) HIPCHK(hipMemcpyAsync(pose, P.pose[0], np * 8, hipMemcpyDeviceToHost, stream));
+  if (ns) HIPCHK(hipMemcpyAsync(sb, P.sb[0], ns * 8, hipMemcpyDeviceToHost, stream));
+  if (nl) HIPCHK(hipMemcpyAsync(lm, P.lm[0], nl * 8, hipMemcpyDeviceToHost, stream));
+  if (ni) HIPCHK(hipMemcpyAsync(imu, P.imu_state, ni * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  forWindows(B.n_win, [&](int w) {
+    const okvisgpu_problem* p = probs[w];
+    const double* q = pose + 7 * (size_t)B.pose_base[w];
+    std::memcpy(p->poses, q, sizeof(double) * 7 * p->n_poses);
+    if (B.win_ext_free[w])  // variable extrinsics are written back like every other block
+      std::memcpy(p->extrinsics, q + 7 * (size_t)p->n_poses, sizeof(double) * 7 * p->n_cameras);
+    std::memcpy(p->speed_biases, sb + 9 * (size_t)B.sb_base[w], sizeof(double) * 9 * p->n_speed_biases);
+    const double* l = lm + 4 * (size_t)B.lm_base[w];
+    const int* perm = &B.lm_perm[B.lm_base[w]];
+    for (int k = 0; k < p->n_landmarks; ++k) std::memcpy(&p->landmarks[4 * (size_t)perm[k]], l + 4 * (size_t)k, 32);
+    if (p->imu_state && p->n_imu)
+      std::memcpy(p->imu_state, imu + (size_t)B.imu_base[w] * kImuState, sizeof(double) * kImuState * p->n_imu);
+  });
+}
+
+// ViGraph::updateLandmarks on the current parameter values (okvisgpu_update_landmarks): every
+// window's current set is gathered into set 0 as downloadParams does (before the first solve
+// WinState is the build's zeroed scratch: xcur = 0, set 0 holds the uploaded values), one kernel
+// over the batch's landmarks, one copy per output into pinned memory, and a threaded scatter into
+// the caller's order (landmarks through lm_perm, observations through obs_orig). Of the caller's
+// problem arrays only the re-placed landmarks are written.
+void okvisgpu_ctx::updateLandmarks(okvisgpu_landmark_update* U) {
+  for (int w = 0; w < B.n_win; ++w) {
+    U[w].n_initialised = U[w].n_reset = 0;
+    U[w].in_front = 1;
+    U[w].reserved = 0;
+  }
+  const size_t nl = (size_t)P.n_lm, no = (size_t)P.n_obs;
+  if (nl == 0) return;  // nothing to launch
+  bool wantErr = false;
+  for (int w = 0; w < B.n_win; ++w) wantErr = wantErr || U[w].obs_error != nullptr;
+  // device: quality [nl] | dirs [no][3] | err [no] | flags [nl]; host: quality [nl] | lm [nl][4] | err [no] | flags [nl]
+  const size_t need = 8 * (nl + 4 * std::max<size_t>(no, 1)) + nl;
+  double* dQ = static_cast<double*>(batchScratch.need(need));
+  double *dDirs = dQ + nl, *dErr = dDirs + 3 * no;
+  uint8_t* dFlags = reinterpret_cast<uint8_t*>(dErr + std::max<size_t>(no, 1));
+  double* hQ = reinterpret_cast<double*>(paramStage(8 * (nl + 4 * nl + no) + nl));
+  double *hLm = hQ + nl, *hErr = hLm + 4 * nl;
+  uint8_t* hFlags = reinterpret_cast<uint8_t*>(hErr + no);
+  launch_select_current(P, stream);
+  launch_update_landmarks(P, dQ, dFlags, dErr, dDirs, stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(hQ, dQ, nl * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(hLm, P.lm[0], 4 * nl * 8, hipMemcpyDeviceToHost, stream));
+  if (wantErr && no) HIPCHK(hipMemcpyAsync(hErr, dErr, no * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(hFlags, dFlags, nl, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  forWindows(B.n_win, [&](int w) {
+    const okvisgpu_problem* p = probs[w];
+    okvisgpu_landmark_update& u = U[w];
+    const size_t lb = (size_t)B.lm_base[w];
+    const int* perm = &B.lm_perm[lb];
+    int nInit = 0, nReset = 0, front = 1;
+    for (int k = 0; k < p->n_landmarks; ++k) {
+      const int l = perm[k];
+      const uint8_t f = hFlags[lb + k];
+      if (u.quality) u.quality[l] = hQ[lb + k];
+      if (u.initialised) u.initialised[l] = (f & kLmInitialised) ? 1 : 0;
+      if (u.reset) u.reset[l] = (f & kLmReset) ? 1 : 0;
+      nInit += (f & kLmInitialised) ? 1 : 0;
+      if (f & kLmNotInFront) front = 0;
+      if (f & kLmReset) {
+        ++nReset;
+        std::memcpy(&p->landmarks[4 * (size_t)l], hLm + 4 * (lb + k), 32);
+      }
+    }
+    u.n_initialised = nInit;
+    u.n_reset = nReset;
+    u.in_front = front;
+    if (u.obs_error) {
+      const size_t ob = (size_t)B.obs_base[w];
+      for (int k = 0; k < p->n_observations; ++k) u.obs_error[B.obs_orig[ob + k]] = hErr[ob + k];
+    }
+  });
+}
+
+// ViGraph::computeCovisibilities on the structure of the last set_problems
+// (okvisgpu_covisibilities): a record per window that has states, landmarks and observations, the
+// record of every 64-landmark word (k_covis_bits' work list), the work lists of the two count
+// kernels (covisFitsLds picks a window's), the caller's exclusion masks
+// permuted into internal landmark order; all of it packed into pinned memory and uploaded as one
+// copy. k_covis_bits writes every word of the bitset and the count kernels every element of
+// counts / n_observed, so nothing is cleared. One copy back per output, then a threaded scatter;
+// the pair and visibility totals are taken on the host. Reads no parameter value and writes neither
+// the caller's problem arrays nor the arena.
+void okvisgpu_ctx::covisibilities(okvisgpu_covisibility* V) {
+  const int nwin = B.n_win;
+  std::vector<CovisWin> recs;
+  std::vector<int> recOf((size_t)nwin, -1);
+  std::vector<int32_t> items0, items1, wordRec;  // wordRec: the record of each 64-landmark word
+  size_t lds0 = 0;
+  int64_t words = 0, bitsTot = 0, cntTot = 0, stateTot = 0;
+  bool anyMask = false;
+  for (int w = 0; w < nwin; ++w) {
+    const okvisgpu_problem* p = probs[w];
+    V[w].n_pairs = V[w].n_visible = V[w].any = V[w].path = 0;
+    if (p->n_poses <= 0 || p->n_landmarks <= 0 || p->n_observations <= 0) {  // all zeros, nothing to launch
+      const size_t S = (size_t)std::max(p->n_poses, 0);
+      if (V[w].counts) std::memset(V[w].counts, 0, 4 * S * S);
+      if (V[w].n_observed) std::memset(V[w].n_observed, 0, 4 * S);
+      if (V[w].visible) std::memset(V[w].visible, 0, S);
+      continue;
+    }
+    CovisWin r{};
+    r.lm_begin = B.lm_base[w];
+    r.n_lm = p->n_landmarks;
+    r.pose_begin = B.pose_base[w];
+    r.n_state = p->n_poses;
+    r.word_begin = (int32_t)words;
+    r.n_words = (p->n_landmarks + 63) / 64;
+    r.state_off = (int32_t)stateTot;
+    r.bits_off = bitsTot;
+    r.counts_off = cntTot;
+    const int idx = (int)recs.size();
+    if (covisFitsLds(r.n_state, r.n_words)) {
+      items0.push_back(idx);
+      lds0 = std::max(lds0, covisLdsBytes(r.n_state, r.n_words));
+    } else {
+      V[w].path = 1;
+      const int T = (r.n_state + kCovisTile - 1) / kCovisTile;
+      for (int ti = 0; ti < T; ++ti)
+        for (int tj = 0; tj <= ti; ++tj) items1.insert(items1.end(), {idx, ti, tj});
+    }
+    wordRec.insert(wordRec.end(), (size_t)r.n_words, idx);
+    words += r.n_words;
+    stateTot += r.n_state;
+    bitsTot += (int64_t)r.n_state * r.n_words;
+    cntTot += (int64_t)r.n_state * r.n_state;
+    anyMask = anyMask || V[w].landmark_excluded != nullptr;
+    recOf[w] = idx;
+    recs.push_back(r);
+  }
+  if (recs.empty()) return;
+
+  // device: uploaded part (records | word records | items0 | items1 | mask), then bits | counts | n_observed
+  const size_t nl = (size_t)P.n_lm;
+  Arena A;
+  const size_t oRec = A.reserve(sizeof(CovisWin) * recs.size()), oWr = A.reserve(4 * wordRec.size()),
+               oI0 = A.reserve(4 * items0.size()), oI1 = A.reserve(4 * items1.size()), oEx = A.reserve(anyMask ? nl : 0);
+  const size_t upBytes = A.size;
+  const size_t oBits = A.reserve(8 * (size_t)bitsTot), oCnt = A.reserve(4 * (size_t)cntTot),
+               oObs = A.reserve(4 * (size_t)stateTot);
+  char* dev = static_cast<char*>(batchScratch.need(A.size));
+  // pinned: the uploaded part as on the device, then counts | n_observed as they come back
+  const size_t hCntOff = (upBytes + 255) & ~size_t(255), hObsOff = hCntOff + 4 * (size_t)cntTot;
+  char* host = paramStage(hObsOff + 4 * (size_t)stateTot);
+  std::memcpy(host + oRec, recs.data(), sizeof(CovisWin) * recs.size());
+  std::memcpy(host + oWr, wordRec.data(), 4 * wordRec.size());
+  if (!items0.empty()) std::memcpy(host + oI0, items0.data(), 4 * items0.size());
+  if (!items1.empty()) std::memcpy(host + oI1, items1.data(), 4 * items1.size());
+  if (anyMask)
     forWindows(nwin, [&](int w) {
-      if (recOf[w] < 0) return;
-      const CovisWin& r = recs[(size_t)recOf[w]];
-      okvisgpu_covisibility& v = V[w];
-      const size_t S = (size_t)r.n_state;
-      const int32_t *c = hCnt + r.counts_off, *o = hObs + r.state_off;
-      if (v.counts) std::memcpy(v.counts, c, 4 * S * S);
-      if (v.n_observed) std::memcpy(v.n_observed, o, 4 * S);
-      int pairs = 0, vis = 0;
-      for (size_t i = 0; i < S; ++i) {
-        vis += o[i] > 0;
-        if (v.visible) v.visible[i] = o[i] > 0 ? 1 : 0;
-        for (size_t j = i + 1; j < S; ++j) pairs += c[i * S + j] > 0;
-      }
-      v.n_pairs = pairs;
-      v.n_visible = vis;
-      v.any = pairs > 0 ? 1 : 0;
+      const okvisgpu_problem* p = probs[w];
+      uint8_t* ex = reinterpret_cast<uint8_t*>(host + oEx) + (size_t)B.lm_base[w];
+      const uint8_t* in = V[w].landmark_excluded;
+      const int* perm = &B.lm_perm[B.lm_base[w]];
+      if (!in) std::memset(ex, 0, (size_t)std::max(p->n_landmarks, 0));
+      else
+        for (int k = 0; k < p->n_landmarks; ++k) ex[k] = in[perm[k]] ? 1 : 0;
     });
-  }
+  HIPCHK(hipMemcpyAsync(dev, host, upBytes, hipMemcpyHostToDevice, stream));
+  const CovisWin* dRec = reinterpret_cast<const CovisWin*>(dev + oRec);
+  unsigned long long* dBits = reinterpret_cast<unsigned long long*>(dev + oBits);
+  int32_t *dCnt = reinterpret_cast<int32_t*>(dev + oCnt), *dObs = reinterpret_cast<int32_t*>(dev + oObs);
+  launch_covis_bits(P, dRec, (int)recs.size(), reinterpret_cast<const int32_t*>(dev + oWr), (int)words,
+                    anyMask ? reinterpret_cast<const uint8_t*>(dev + oEx) : nullptr, dBits, stream);
+  launch_covis_counts(dRec, reinterpret_cast<const int32_t*>(dev + oI0), (int)items0.size(), lds0,
+                      reinterpret_cast<const int32_t*>(dev + oI1), (int)(items1.size() / 3), dBits, dCnt, dObs, stream);
+  HIPCHK(hipGetLastError());
+  const int32_t* hCnt = reinterpret_cast<const int32_t*>(host + hCntOff);
+  const int32_t* hObs = reinterpret_cast<const int32_t*>(host + hObsOff);
+  HIPCHK(hipMemcpyAsync(host + hCntOff, dCnt, 4 * (size_t)cntTot, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(host + hObsOff, dObs, 4 * (size_t)stateTot, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  forWindows(nwin, [&](int w) {
+    if (recOf[w] < 0) return;
+    const CovisWin& r = recs[(size_t)recOf[w]];
+    okvisgpu_covisibility& v = V[w];
+    const size_t S = (size_t)r.n_state;
+    const int32_t *c = hCnt + r.counts_off, *o = hObs + r.state_off;
+    if (v.counts) std::memcpy(v.counts, c, 4 * S * S);
+    if (v.n_observed) std::memcpy(v.n_observed, o, 4 * S);
+    int pairs = 0, vis = 0;
+    for (size_t i = 0; i < S; ++i) {
+      vis += o[i] > 0;
+      if (v.visible) v.visible[i] = o[i] > 0 ? 1 : 0;
+      for (size_t j = i + 1; j < S; ++j) pairs += c[i * S + j] > 0;
+    }
+    v.n_pairs = pairs;
+    v.n_visible = vis;
+    v.any = pairs > 0 ? 1 : 0;
+  });
+}
 
-  std::vector<WinState> readStates() {
-    std::vector<WinState> s(P.n_win);
-    HIPCHK(hipMemcpyAsync(s.data(), P.st, sizeof(WinState) * s.size(), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    return s;
-  }
+std::vector<WinState> okvisgpu_ctx::readStates() {
+  std::vector<WinState> s(P.n_win);
+  HIPCHK(hipMemcpyAsync(s.data(), P.st, sizeof(WinState) * s.size(), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return s;
+}
 
-  void launchInit(int evalMode) {
-    evalAll(evalMode, stream);
-    launch_reduce(P, R_COST_INIT, stream);
-    launch_lm_blocks(P, 0, stream);
-    launch_imu_hess(P, 0, stream);
-    launch_fgrad(P, 0, stream);
-    launch_gradnorm(P, 0, stream);
-    if (regime.lin_prep) launch_lm_prep(P, stream);  // (the first iteration's; later ones: k_lin_few, runTimed)
-    HIPCHK(hipGetLastError());
-  }
+void okvisgpu_ctx::launchInit(int evalMode) {
+  evalAll(evalMode, stream);
+  launch_reduce(P, R_COST_INIT, stream);
+  launch_lm_blocks(P, 0, stream);
+  launch_imu_hess(P, 0, stream);
+  launch_fgrad(P, 0, stream);
+  launch_gradnorm(P, 0, stream);
+  if (regime.lin_prep) launch_lm_prep(P, stream);  // (the first iteration's; later ones: k_lin_few, runTimed)
+  HIPCHK(hipGetLastError());
+}
 
-  // ---- one trust-region iteration: a table of steps, walked by three executors -------------------
-  // A step is a launcher, the ABI phase its device time is booked to (kPhaseNames) and the lane it
-  // may run on: a step on a side lane is independent of the main-lane step before it and of the
-  // other side lane's (disjoint data: pose-pose vs. speed/bias blocks of S; observation / IMU, prior
-  // and edge / host-factor records; landmark groups vs. IMU Hessians), so a main-lane step and the
-  // side-lane steps after it are one fork / join group.
-  enum Lane { MAIN = 0, SIDE0 = 1, SIDE1 = 2 };
-  struct Step {
-    void (*launch)(okvisgpu_ctx& c, hipStream_t s);
-    int phase, lane;
-  };
+// ---- one trust-region iteration: a table of steps, walked by three executors -------------------
+// A step is a launcher, the ABI phase its device time is booked to (kPhaseNames) and the lane it
+// may run on: a step on a side lane is independent of the main-lane step before it and of the
+// other side lane's (disjoint data: pose-pose vs. speed/bias blocks of S; observation / IMU, prior
+// and edge / host-factor records; landmark groups vs. IMU Hessians), so a main-lane step and the
+// side-lane steps after it are one fork / join group.
 #define STEP(phase, lane, call) Step{[](okvisgpu_ctx& c, hipStream_t s) { call; }, phase, lane}
-  // The iteration of every batch but a few windows on one stream, and of every eager iteration (the
-  // ABI's phases and the four Summary sums are per kernel, so the timed iteration stays unfused also
-  // where the solve it reports on runs fewSteps(): the same device code on the same data in the same
-  // order per buffer, and runTimed() closes with the prep that fewSteps() expects: the same bits,
-  // also when eager and captured iterations alternate in one solve). Phases 1 zero_S, 5 gn_finalize, 6 jv and 7 reduce_jv no longer
-  // launch (S is cleared once per build; the others run inside cholesky, lm_backsub and dogleg): they
-  // stay in the ABI's list and report 0.
-  static const std::vector<Step>& unfusedSteps() {
-    static const std::vector<Step> t = {
-        STEP(0, MAIN, launch_lm_prep(c.P, s)),  // GN prep: only windows whose Z is stale
-        STEP(2, MAIN, launch_assemble_pp(c.P, s)),
-        STEP(2, SIDE0, launch_assemble_sb(c.P, s)),
-        STEP(3, MAIN, launch_cholesky(c.P, s)),    // (with the f-blocks' GN vectors)
-        STEP(4, MAIN, launch_lm_backsub(c.P, s)),  // (with the dogleg vectors and every J*v)
-        STEP(8, MAIN, launch_dogleg(c.P, s)),
-        STEP(9, MAIN, launch_eval_obs(c.P, 1, s)),  // candidate evaluation
-        STEP(10, SIDE0, launch_eval_imu(c.P, 1, s)),  // (with the priors and edges)
-        STEP(11, SIDE1, c.evalHost(1, s)),
-        STEP(12, MAIN, launch_reduce(c.P, R_COST_CAND, s)),
-        STEP(13, MAIN, launch_lm_blocks(c.P, 1, s)),  // linearisation at the accepted point
-        STEP(13, SIDE0, launch_imu_hess(c.P, 1, s)),
-        STEP(13, MAIN, launch_fgrad(c.P, 1, s)),
-        STEP(14, MAIN, launch_gradnorm(c.P, 1, s)),
-    };
-    return t;
-  }
-  // Few windows on one stream (regime.fused_gradnorm; a latency chain of small launches): the
-  // independent kernels of a group as one launch, the GN prep inside the linearisation launch unless
-  // regime.lin_prep is off (then captureIterations() puts launch_lm_prep in front), and the
-  // gradient test of an iteration inside the next iteration's assembly launch (k_assemble_few; it
-  // reads nothing the assembly writes, and a window it ends is skipped from the Cholesky on).
-  // Invariant (prepPending()): with the prep inside the linearisation, this list starts from Z, L^-1
-  // and partial Schur blocks already formed for every window's current mu, so whatever ran before it
-  // (launchInit, the list itself, an eager iteration) must have ended with the prep of the windows
-  // whose step was not accepted: a mu raised by a failed Cholesky or an invalid step is otherwise
-  // assembled with operands of the old mu. The captured graph ends with one standalone test, so that every graph launch leaves complete window
-  // states; the test is idempotent (the same state gives the same norms and decision), so the
-  // repeat at the start of the next graph launch is harmless.
-  static const std::vector<Step>& fewSteps() {
-    static const std::vector<Step> t = {
-        STEP(2, MAIN, launch_assemble_gradnorm_few(c.P, s)),
-        STEP(3, MAIN, launch_cholesky(c.P, s)),
-        STEP(4, MAIN, launch_lm_backsub(c.P, s)),
-        STEP(8, MAIN, launch_dogleg(c.P, s)),
-        STEP(9, MAIN, launch_eval_few(c.P, 1, s)),
-        STEP(11, MAIN, c.evalHost(1, s)),
-        STEP(12, MAIN, launch_reduce(c.P, R_COST_CAND, s)),
-        STEP(13, MAIN, launch_lin_few(c.P, s)),
-        STEP(13, MAIN, launch_fgrad(c.P, 1, s)),
-    };
-    return t;
-  }
+// The iteration of every batch but a few windows on one stream, and of every eager iteration (the
+// ABI's phases and the four Summary sums are per kernel, so the timed iteration stays unfused also
+// where the solve it reports on runs fewSteps(): the same device code on the same data in the same
+// order per buffer, and runTimed() closes with the prep that fewSteps() expects: the same bits,
+// also when eager and captured iterations alternate in one solve). Phases 1 zero_S, 5 gn_finalize, 6 jv and 7 reduce_jv no longer
+// launch (S is cleared once per build; the others run inside cholesky, lm_backsub and dogleg): they
+// stay in the ABI's list and report 0.
+const std::vector<okvisgpu_ctx::Step>& okvisgpu_ctx::unfusedSteps() {
+  static const std::vector<Step> t = {
+      STEP(0, MAIN, launch_lm_prep(c.P, s)),  // GN prep: only windows whose Z is stale
+      STEP(2, MAIN, launch_assemble_pp(c.P, s)),
+      STEP(2, SIDE0, launch_assemble_sb(c.P, s)),
+      STEP(3, MAIN, launch_cholesky(c.P, s)),    // (with the f-blocks' GN vectors)
+      STEP(4, MAIN, launch_lm_backsub(c.P, s)),  // (with the dogleg vectors and every J*v)
+      STEP(8, MAIN, launch_dogleg(c.P, s)),
+      STEP(9, MAIN, launch_eval_obs(c.P, 1, s)),  // candidate evaluation
+      STEP(10, SIDE0, launch_eval_imu(c.P, 1, s)),  // (with the priors and edges)
+      STEP(11, SIDE1, c.evalHost(1, s)),
+      STEP(12, MAIN, launch_reduce(c.P, R_COST_CAND, s)),
+      STEP(13, MAIN, launch_lm_blocks(c.P, 1, s)),  // linearisation at the accepted point
+      STEP(13, SIDE0, launch_imu_hess(c.P, 1, s)),
+      STEP(13, MAIN, launch_fgrad(c.P, 1, s)),
+      STEP(14, MAIN, launch_gradnorm(c.P, 1, s)),
+  };
+  return t;
+}
+// Few windows on one stream (regime.fused_gradnorm; a latency chain of small launches): the
+// independent kernels of a group as one launch, the GN prep inside the linearisation launch unless
+// regime.lin_prep is off (then captureIterations() puts launch_lm_prep in front), and the
+// gradient test of an iteration inside the next iteration's assembly launch (k_assemble_few; it
+// reads nothing the assembly writes, and a window it ends is skipped from the Cholesky on).
+// Invariant (prepPending()): with the prep inside the linearisation, this list starts from Z, L^-1
+// and partial Schur blocks already formed for every window's current mu, so whatever ran before it
+// (launchInit, the list itself, an eager iteration) must have ended with the prep of the windows
+// whose step was not accepted: a mu raised by a failed Cholesky or an invalid step is otherwise
+// assembled with operands of the old mu. The captured graph ends with one standalone test, so that every graph launch leaves complete window
+// states; the test is idempotent (the same state gives the same norms and decision), so the
+// repeat at the start of the next graph launch is harmless.
+const std::vector<okvisgpu_ctx::Step>& okvisgpu_ctx::fewSteps() {
+  static const std::vector<Step> t = {
+      STEP(2, MAIN, launch_assemble_gradnorm_few(c.P, s)),
+      STEP(3, MAIN, launch_cholesky(c.P, s)),
+      STEP(4, MAIN, launch_lm_backsub(c.P, s)),
+      STEP(8, MAIN, launch_dogleg(c.P, s)),
+      STEP(9, MAIN, launch_eval_few(c.P, 1, s)),
+      STEP(11, MAIN, c.evalHost(1, s)),
+      STEP(12, MAIN, launch_reduce(c.P, R_COST_CAND, s)),
+      STEP(13, MAIN, launch_lin_few(c.P, s)),
+      STEP(13, MAIN, launch_fgrad(c.P, 1, s)),
+  };
+  return t;
+}
 #undef STEP
 
-  // fewSteps() follows and will not start with the GN prep: what runs before it must end with one
-  bool prepPending() const { return regime.fused_gradnorm && regime.lin_prep; }
+// Serial executor (one-stream capture): the lanes are ignored.
+void okvisgpu_ctx::runSerial(const std::vector<Step>& steps) {
+  for (const Step& st : steps) st.launch(*this, stream);
+}
+// Forked executor (capture with fork streams, so the graph runs a group's kernels concurrently):
+// per group, the side lanes wait for an event of the main stream, the side-lane steps are
+// captured, then the main-lane step, and the main stream waits for an event of each side lane.
+// Every fork and join of one capture has its own event.
+void okvisgpu_ctx::runForked(const std::vector<Step>& steps) {
+  hipStream_t lane[3] = {stream, side[0], side[1]};
+  auto edge = [&](hipStream_t from, hipStream_t to) {
+    if (forkEvUsed == forkEv.size()) {
+      hipEvent_t e;
+      HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      forkEv.push_back(e);
+    }
+    hipEvent_t e = forkEv[forkEvUsed++];
+    HIPCHK(hipEventRecord(e, from));
+    HIPCHK(hipStreamWaitEvent(to, e, 0));
+  };
+  for (size_t i = 0, j; i < steps.size(); i = j) {
+    for (j = i + 1; j < steps.size() && steps[j].lane != MAIN;) ++j;
+    for (size_t k = i + 1; k < j; ++k) edge(stream, lane[steps[k].lane]);
+    for (size_t k = i + 1; k < j; ++k) steps[k].launch(*this, lane[steps[k].lane]);
+    steps[i].launch(*this, stream);
+    for (size_t k = i + 1; k < j; ++k) edge(lane[steps[k].lane], stream);
+  }
+}
+// Eager executor (okvisgpu_profile_iteration and the verbose solve): the unfused steps on the
+// context's stream with a HIP event after each; ms[phase] += the step's device time. Where the
+// captured graph is fewSteps() the iteration closes with the GN prep (the first step again, phase
+// 0), as k_lin_few does there: captured iterations may follow.
+void okvisgpu_ctx::runTimed(double* ms) {
+  std::vector<Step> steps = unfusedSteps();
+  if (prepPending()) steps.push_back(steps.front());
+  std::vector<hipEvent_t> ev(steps.size() + 1);
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipEventRecord(ev[0], stream));
+  for (size_t i = 0; i < steps.size(); ++i) {
+    steps[i].launch(*this, stream);
+    HIPCHK(hipEventRecord(ev[i + 1], stream));
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(stream));
+  for (size_t i = 0; i < steps.size(); ++i) {
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+    ms[steps[i].phase] += t;
+  }
+  for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+}
 
-  // Serial executor (one-stream capture): the lanes are ignored.
-  void runSerial(const std::vector<Step>& steps) {
-    for (const Step& st : steps) st.launch(*this, stream);
+// k iterations captured as one graph, as the regime lays them out
+hipGraphExec_t okvisgpu_ctx::captureIterations(int k) {
+  hipGraph_t g;
+  hipGraphExec_t exec = nullptr;
+  HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+  forkEvUsed = 0;
+  for (int i = 0; i < k; ++i) {
+    if (regime.fused_gradnorm && !prepPending()) launch_lm_prep(P, stream);
+    if (regime.fused_gradnorm) runSerial(fewSteps());
+    else if (regime.serial_graph) runSerial(unfusedSteps());
+    else runForked(unfusedSteps());
   }
-  // Forked executor (capture with fork streams, so the graph runs a group's kernels concurrently):
-  // per group, the side lanes wait for an event of the main stream, the side-lane steps are
-  // captured, then the main-lane step, and the main stream waits for an event of each side lane.
-  // Every fork and join of one capture has its own event.
-  void runForked(const std::vector<Step>& steps) {
-    hipStream_t lane[3] = {stream, side[0], side[1]};
-    auto edge = [&](hipStream_t from, hipStream_t to) {
-      if (forkEvUsed == forkEv.size()) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        forkEv.push_back(e);
-      }
-      hipEvent_t e = forkEv[forkEvUsed++];
-      HIPCHK(hipEventRecord(e, from));
-      HIPCHK(hipStreamWaitEvent(to, e, 0));
-    };
-    for (size_t i = 0, j; i < steps.size(); i = j) {
-      for (j = i + 1; j < steps.size() && steps[j].lane != MAIN;) ++j;
-      for (size_t k = i + 1; k < j; ++k) edge(stream, lane[steps[k].lane]);
-      for (size_t k = i + 1; k < j; ++k) steps[k].launch(*this, lane[steps[k].lane]);
-      steps[i].launch(*this, stream);
-      for (size_t k = i + 1; k < j; ++k) edge(lane[steps[k].lane], stream);
-    }
+  if (regime.fused_gradnorm) launch_gradnorm(P, 1, stream);
+  HIPCHK(hipStreamEndCapture(stream, &g));
+  HIPCHK(hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
+  HIPCHK(hipGraphDestroy(g));
+  return exec;
+}
+void okvisgpu_ctx::ensureGraph() {
+  if (iterGraph) return;
+  iterGraph = captureIterations(1);
+  if (regime.graph_iters > 1) {
+    iterGraphK = captureIterations(regime.graph_iters);
+    graphIters = regime.graph_iters;
   }
-  // Eager executor (okvisgpu_profile_iteration and the verbose solve): the unfused steps on the
-  // context's stream with a HIP event after each; ms[phase] += the step's device time. Where the
-  // captured graph is fewSteps() the iteration closes with the GN prep (the first step again, phase
-  // 0), as k_lin_few does there: captured iterations may follow.
-  void runTimed(double* ms) {
-    std::vector<Step> steps = unfusedSteps();
-    if (prepPending()) steps.push_back(steps.front());
-    std::vector<hipEvent_t> ev(steps.size() + 1);
-    for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipEventRecord(ev[0], stream));
-    for (size_t i = 0; i < steps.size(); ++i) {
-      steps[i].launch(*this, stream);
-      HIPCHK(hipEventRecord(ev[i + 1], stream));
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(stream));
-    for (size_t i = 0; i < steps.size(); ++i) {
-      float t = 0.f;
-      HIPCHK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-      ms[steps[i].phase] += t;
-    }
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
-
-  // k iterations captured as one graph, as the regime lays them out
-  hipGraphExec_t captureIterations(int k) {
-    hipGraph_t g;
-    hipGraphExec_t exec = nullptr;
-    HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    forkEvUsed = 0;
-    for (int i = 0; i < k; ++i) {
-      if (regime.fused_gradnorm && !prepPending()) launch_lm_prep(P, stream);
-      if (regime.fused_gradnorm) runSerial(fewSteps());
-      else if (regime.serial_graph) runSerial(unfusedSteps());
-      else runForked(unfusedSteps());
-    }
-    if (regime.fused_gradnorm) launch_gradnorm(P, 1, stream);
-    HIPCHK(hipStreamEndCapture(stream, &g));
-    HIPCHK(hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
-    HIPCHK(hipGraphDestroy(g));
-    return exec;
-  }
-  void ensureGraph() {
-    if (iterGraph) return;
-    iterGraph = captureIterations(1);
-    if (regime.graph_iters > 1) {
-      iterGraphK = captureIterations(regime.graph_iters);
-      graphIters = regime.graph_iters;
-    }
-  }
-};
+}
 
 namespace {
-
 thread_local std::string g_err;
+}
 
-int fail(okvisgpu_ctx* c, int code, const std::string& m) {
+int okg::fail(okvisgpu_ctx* c, int code, const std::string& m) {
   if (c) c->last_error = m;
   g_err = m;
   return code;
 }
-
-template <class F>
-int guarded(okvisgpu_ctx* c, F f) {
-  try {
-    return f();
-  } catch (const HipError& e) {
-    return fail(c, e.code, e.msg);
-  } catch (const ArgError& e) {
-    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, e.msg);
-  } catch (const UnsupportedError& e) {
-    return fail(c, OKVISGPU_ERR_UNSUPPORTED, e.msg);
-  } catch (const std::bad_alloc&) {
-    return fail(c, OKVISGPU_ERR_OUT_OF_MEMORY, "host allocation failed");
-  } catch (const std::exception& e) {
-    return fail(c, OKVISGPU_ERR_DEVICE, e.what());
-  }
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -1799,691 +1592,6 @@ int okvisgpu_eval_host(okvisgpu_ctx* c, int32_t window, double* r, double* J) {
   });
 }
 
-int okvisgpu_imu_append(okvisgpu_ctx* c, const okvisgpu_imu_append_batch* A, int32_t* steps) {
-  if (!c || !A || A->n < 0) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "imu_append: bad arguments");
-  if (A->n == 0) return OKVISGPU_OK;
-  if (!A->state || !A->t1_old_ns || !A->t1_new_ns || !A->speed_biases || !A->sample_begin)
-    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "imu_append: missing arrays");
-  return guarded(c, [&]() {
-    HIPCHK(hipSetDevice(c->device));
-    const int n = A->n;
-    if (A->sample_begin[0] != 0) throw ArgError{"imu_append: sample_begin must start at 0"};
-    for (int i = 0; i < n; ++i)
-      if (A->sample_begin[i + 1] < A->sample_begin[i]) throw ArgError{"imu_append: sample_begin not monotone"};
-    const int ns = A->sample_begin[n];
-    if (ns && (!A->sample_t_ns || !A->sample_gyr_acc)) throw ArgError{"imu_append: sample arrays missing"};
-    std::vector<int32_t> blk(4 * (size_t)n);
-    for (int i = 0; i < n; ++i) { blk[4 * i] = 0; blk[4 * i + 1] = i; blk[4 * i + 2] = 0; blk[4 * i + 3] = i; }
-    const okvisgpu_imu_params& ip = A->imu_params;
-    const double par[7] = {ip.a_max, ip.g_max, ip.sigma_g_c, ip.sigma_a_c, ip.sigma_gw_c, ip.sigma_aw_c, ip.g};
-    Arena M;
-    const size_t o_blk = M.reserve(blk.size() * 4), o_t0 = M.reserve(8 * (size_t)n), o_t1 = M.reserve(8 * (size_t)n),
-                 o_sb = M.reserve(4 * (size_t)(n + 1)), o_ts = M.reserve(8 * (size_t)std::max(1, ns)),
-                 o_ga = M.reserve(48 * (size_t)std::max(1, ns)), o_par = M.reserve(sizeof(par)),
-                 o_st = M.reserve(sizeof(double) * kImuState * n), o_bias = M.reserve(72 * (size_t)n),
-                 o_self = M.reserve(sizeof(DevProblem));
-    char* base = nullptr;
-    HIPCHK(hipMalloc(&base, M.size));
-    std::unique_ptr<char, void (*)(char*)> guard(base, [](char* p) { (void)hipFree(p); });
-    auto up = [&](size_t off, const void* src, size_t bytes) {
-      if (bytes) HIPCHK(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, c->stream));
-    };
-    up(o_blk, blk.data(), blk.size() * 4);
-    up(o_t0, A->t1_old_ns, 8 * (size_t)n);
-    up(o_t1, A->t1_new_ns, 8 * (size_t)n);
-    up(o_sb, A->sample_begin, 4 * (size_t)(n + 1));
-    up(o_ts, A->sample_t_ns, 8 * (size_t)ns);
-    up(o_ga, A->sample_gyr_acc, 48 * (size_t)ns);
-    up(o_par, par, sizeof(par));
-    up(o_st, A->state, sizeof(double) * kImuState * n);
-    up(o_bias, A->speed_biases, 72 * (size_t)n);
-    // a descriptor holding only what the append mode of k_eval_imu reads
-    DevProblem D{};
-    D.n_imu = n;
-    D.n_fac = n;
-    D.imu_blocks = reinterpret_cast<const int32_t*>(base + o_blk);
-    D.imu_t0 = reinterpret_cast<const int64_t*>(base + o_t0);
-    D.imu_t1 = reinterpret_cast<const int64_t*>(base + o_t1);
-    D.imu_sbegin = reinterpret_cast<const int32_t*>(base + o_sb);
-    D.imu_ts = reinterpret_cast<const int64_t*>(base + o_ts);
-    D.imu_ga = reinterpret_cast<const double*>(base + o_ga);
-    D.imu_par = reinterpret_cast<const double*>(base + o_par);
-    D.imu_state = reinterpret_cast<double*>(base + o_st);
-    D.sb[0] = D.sb[1] = reinterpret_cast<double*>(base + o_bias);
-    D.self = reinterpret_cast<const DevProblem*>(base + o_self);
-    up(o_self, &D, sizeof(D));
-    launch_imu_append(D, c->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(A->state, D.imu_state, sizeof(double) * kImuState * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (steps)
-      for (int i = 0; i < n; ++i) {
-        const int s0 = A->sample_begin[i], s1 = A->sample_begin[i + 1];
-        const bool covered = s1 > s0 && A->sample_t_ns[s1 - 1] >= A->t1_new_ns[i];
-        steps[i] = covered ? (int32_t)A->state[(size_t)i * kImuState + 291] : -1;
-      }
-    return (int)OKVISGPU_OK;
-  });
-}
-
-int okvisgpu_imu_propagate(okvisgpu_ctx* c, const okvisgpu_imu_propagate_batch* A, int32_t* steps) {
-  if (!c || !A || A->n < 0) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "imu_propagate: bad arguments");
-  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "imu_propagate: call after solve_end");
-  if (A->n == 0) return OKVISGPU_OK;
-  if (!A->poses || !A->speed_biases || !A->t_start_ns || !A->t_end_ns || !A->sample_begin || !A->sample_t_ns ||
-      !A->sample_gyr_acc)
-    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "imu_propagate: missing arrays");
-  return guarded(c, [&]() {
-    const size_t n = (size_t)A->n;
-    if (A->sample_begin[0] != 0) throw ArgError{"imu_propagate: sample_begin must start at 0"};
-    for (size_t i = 0; i < n; ++i)
-      if (A->sample_begin[i + 1] < A->sample_begin[i]) throw ArgError{"imu_propagate: sample_begin not monotone"};
-    for (size_t i = 0; i < n; ++i) {  // the reference's assertion (ImuError.cpp:550)
-      const int32_t s0 = A->sample_begin[i];
-      if (A->sample_begin[i + 1] == s0) throw ArgError{"imu_propagate: item " + std::to_string(i) + " has no samples"};
-      if (A->sample_t_ns[s0] > A->t_start_ns[i])
-        throw ArgError{"imu_propagate: item " + std::to_string(i) + ": first sample " + std::to_string(A->sample_t_ns[s0]) +
-                       " !<= t_start " + std::to_string(A->t_start_ns[i])};
-    }
-    HIPCHK(hipSetDevice(c->device));
-    const size_t ns = (size_t)A->sample_begin[n];
-    // device and pinned staging share one layout: uploaded [0, upEnd), read back [downBegin, size)
-    Arena M;
-    const size_t o_t0 = M.reserve(8 * n), o_t1 = M.reserve(8 * n), o_sbeg = M.reserve(4 * (n + 1)),
-                 o_ts = M.reserve(8 * ns), o_ga = M.reserve(48 * ns), o_pose = M.reserve(56 * n), o_sb = M.reserve(72 * n);
-    const size_t upEnd = M.size, downBegin = o_pose;
-    const size_t o_steps = M.reserve(4 * n), o_cov = A->covariance ? M.reserve(1800 * n) : 0,
-                 o_jac = A->jacobian ? M.reserve(1800 * n) : 0;
-    if (M.size > c->propScratchBytes) {
-      if (c->propScratch) HIPCHK(hipFree(c->propScratch));
-      c->propScratch = nullptr;
-      c->propScratchBytes = 0;
-      HIPCHK(hipMalloc(&c->propScratch, M.size));
-      c->propScratchBytes = M.size;
-    }
-    char* dev = static_cast<char*>(c->propScratch);
-    char* host = c->paramStage(M.size);
-    std::memcpy(host + o_t0, A->t_start_ns, 8 * n);
-    std::memcpy(host + o_t1, A->t_end_ns, 8 * n);
-    std::memcpy(host + o_sbeg, A->sample_begin, 4 * (n + 1));
-    std::memcpy(host + o_ts, A->sample_t_ns, 8 * ns);
-    std::memcpy(host + o_ga, A->sample_gyr_acc, 48 * ns);
-    std::memcpy(host + o_pose, A->poses, 56 * n);
-    std::memcpy(host + o_sb, A->speed_biases, 72 * n);
-    HIPCHK(hipMemcpyAsync(dev, host, upEnd, hipMemcpyHostToDevice, c->stream));
-    ImuPropagateDev D{};
-    D.n = A->n;
-    const okvisgpu_imu_params& ip = A->imu_params;
-    const double par[7] = {ip.a_max, ip.g_max, ip.sigma_g_c, ip.sigma_a_c, ip.sigma_gw_c, ip.sigma_aw_c, ip.g};
-    std::memcpy(D.par, par, sizeof(par));
-    D.poses = reinterpret_cast<double*>(dev + o_pose);
-    D.sb = reinterpret_cast<double*>(dev + o_sb);
-    D.t_start = reinterpret_cast<const int64_t*>(dev + o_t0);
-    D.t_end = reinterpret_cast<const int64_t*>(dev + o_t1);
-    D.sbegin = reinterpret_cast<const int32_t*>(dev + o_sbeg);
-    D.ts = reinterpret_cast<const int64_t*>(dev + o_ts);
-    D.ga = reinterpret_cast<const double*>(dev + o_ga);
-    D.cov = A->covariance ? reinterpret_cast<double*>(dev + o_cov) : nullptr;
-    D.jac = A->jacobian ? reinterpret_cast<double*>(dev + o_jac) : nullptr;
-    D.steps = reinterpret_cast<int32_t*>(dev + o_steps);
-    launch_imu_propagate(D, c->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host + downBegin, dev + downBegin, M.size - downBegin, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    // an uncovered item's rows stay the caller's (poses and speed/biases come back as they went up;
-    // the covariance and Jacobian rows of such an item were never written on the device)
-    const int32_t* st = reinterpret_cast<const int32_t*>(host + o_steps);
-    std::memcpy(A->poses, host + o_pose, 56 * n);
-    std::memcpy(A->speed_biases, host + o_sb, 72 * n);
-    for (size_t i = 0; i < n; ++i) {
-      if (st[i] < 0) continue;
-      if (A->covariance) std::memcpy(A->covariance + 225 * i, host + o_cov + 1800 * i, 1800);
-      if (A->jacobian) std::memcpy(A->jacobian + 225 * i, host + o_jac + 1800 * i, 1800);
-    }
-    if (steps) std::memcpy(steps, st, 4 * n);
-    return (int)OKVISGPU_OK;
-  });
-}
-
-int okvisgpu_match_to_map(okvisgpu_ctx* c, const okvisgpu_match_batch* A, okvisgpu_match_result* R) {
-  if (!c || !A || !R) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_to_map: bad arguments");
-  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_to_map: call after solve_end");
-  if (A->n_jobs < 0 || A->n_landmarks < 0 || A->n_poses < 0 || A->n_cameras < 0)
-    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_to_map: negative count");
-  if (A->n_jobs == 0) return OKVISGPU_OK;
-  return guarded(c, [&]() {
-    const std::string who = "match_to_map: ";
-    const size_t nj = (size_t)A->n_jobs, nl = (size_t)A->n_landmarks, nc = (size_t)A->n_cameras;
-    if (!A->job_camera || !A->job_pass || !A->job_pose_prepare || !A->job_pose_match || !A->kp_begin)
-      throw ArgError{who + "job arrays missing"};
-    if (!nc || !A->cameras || !A->extrinsics) throw ArgError{who + "cameras missing"};
-    if (A->kp_begin[0] != 0) throw ArgError{who + "kp_begin must start at 0"};
-    for (size_t j = 0; j < nj; ++j)
-      if (A->kp_begin[j + 1] < A->kp_begin[j]) throw ArgError{who + "kp_begin not monotone at job " + std::to_string(j)};
-    const size_t nk = (size_t)A->kp_begin[nj];
-    if (nk && (!A->keypoint || !A->descriptor || !A->ray || !A->ray_valid || !A->landmark))
-      throw ArgError{who + "keypoint arrays missing"};
-    if (nl && (!A->landmarks || !A->landmark_quality || !A->obs_begin)) throw ArgError{who + "landmark arrays missing"};
-    if (nl && A->obs_begin[0] != 0) throw ArgError{who + "obs_begin must start at 0"};
-    for (size_t l = 0; l < nl; ++l)
-      if (A->obs_begin[l + 1] < A->obs_begin[l])
-        throw ArgError{who + "obs_begin not monotone at landmark " + std::to_string(l)};
-    const size_t no = nl ? (size_t)A->obs_begin[nl] : 0;
-    if (no && (!A->obs_pose || !A->obs_camera || !A->obs_descriptor || !A->obs_ray || !A->poses))
-      throw ArgError{who + "observation arrays missing"};
-    for (size_t o = 0; o < no; ++o) {
-      if (A->obs_pose[o] < 0 || A->obs_pose[o] >= A->n_poses)
-        throw ArgError{who + "obs_pose out of range at observation " + std::to_string(o)};
-      if (A->obs_camera[o] < 0 || A->obs_camera[o] >= A->n_cameras)
-        throw ArgError{who + "obs_camera out of range at observation " + std::to_string(o)};
-    }
-    size_t nk0 = 0;
-    for (size_t j = 0; j < nj; ++j) {
-      if (A->job_camera[j] < 0 || A->job_camera[j] >= A->n_cameras)
-        throw ArgError{who + "job_camera out of range at job " + std::to_string(j)};
-      if (A->job_pass[j] != 0 && A->job_pass[j] != 1) throw ArgError{who + "job_pass not 0 / 1 at job " + std::to_string(j)};
-      if (A->job_pass[j] == 0) nk0 += (size_t)(A->kp_begin[j + 1] - A->kp_begin[j]);
-    }
-    for (size_t k = 0; k < nk; ++k)
-      if (A->landmark[k] < -1 || A->landmark[k] >= A->n_landmarks)
-        throw ArgError{who + "carried landmark out of range at keypoint " + std::to_string(k)};
-    std::vector<double> cam((size_t)kMatchCamDoubles * nc);
-    for (size_t k = 0; k < nc; ++k) {
-      const okvisgpu_camera& q = A->cameras[k];
-      if (q.distortion < 0 || q.distortion > 3) throw ArgError{who + "unknown distortion model of camera " + std::to_string(k)};
-      const double cv[kMatchCamDoubles] = {(double)q.distortion, q.fu, q.fv, q.cu, q.cv, q.dist[0], q.dist[1], q.dist[2],
-                                           q.dist[3], q.dist[4], q.dist[5], q.dist[6], q.dist[7], (double)q.width,
-                                           (double)q.height};
-      std::memcpy(&cam[kMatchCamDoubles * k], cv, sizeof(cv));
-    }
-    HIPCHK(hipSetDevice(c->device));
-    // device and pinned staging share one layout: uploaded [0, upEnd), read back [downBegin, downEnd),
-    // then the per-slot scratch only the device holds
-    const size_t njl = nj * nl;
-    Arena M;
-    const size_t o_pose = M.reserve(56 * (size_t)A->n_poses), o_cam = M.reserve(8 * cam.size()), o_ext = M.reserve(56 * nc),
-                 o_lm = M.reserve(32 * nl), o_q = M.reserve(8 * nl), o_use = M.reserve(nl), o_ob = M.reserve(4 * (nl + 1)),
-                 o_op = M.reserve(4 * no), o_oc = M.reserve(4 * no), o_od = M.reserve(48 * no), o_or = M.reserve(24 * no),
-                 o_jc = M.reserve(4 * nj), o_jp = M.reserve(56 * nj), o_jm = M.reserve(56 * nj), o_kl = M.reserve(4 * nk),
-                 o_kj = M.reserve(4 * nk), o_kxy = M.reserve(16 * nk), o_kd = M.reserve(48 * nk), o_kr = M.reserve(24 * nk),
-                 o_kv = M.reserve(nk), o_klm = M.reserve(4 * nk);
-    const size_t upEnd = M.size;
-    const size_t o_cn = M.reserve(4 * njl), downBegin = o_cn, o_c3 = M.reserve(njl), o_co = M.reserve(12 * njl),
-                 o_cp = M.reserve(16 * njl), o_m = M.reserve(4 * nk), o_d = M.reserve(4 * nk), o_r = M.reserve(4 * nk),
-                 o_s = M.reserve(8 * nk), o_pt = M.reserve(32 * nk);
-    const size_t downEnd = M.size;
-    const size_t o_geo = M.reserve(144 * njl), o_desc = M.reserve(144 * njl);
-    if (M.size > c->matchScratchBytes) {
-      if (c->matchScratch) HIPCHK(hipFree(c->matchScratch));
-      c->matchScratch = nullptr;
-      c->matchScratchBytes = 0;
-      HIPCHK(hipMalloc(&c->matchScratch, M.size));
-      c->matchScratchBytes = M.size;
-    }
-    char* dev = static_cast<char*>(c->matchScratch);
-    char* host = c->paramStage(downEnd);
-    auto put = [&](size_t off, const void* src, size_t bytes) {
-      if (bytes) std::memcpy(host + off, src, bytes);
-    };
-    put(o_pose, A->poses, 56 * (size_t)A->n_poses);
-    put(o_cam, cam.data(), 8 * cam.size());
-    put(o_ext, A->extrinsics, 56 * nc);
-    put(o_lm, A->landmarks, 32 * nl);
-    put(o_q, A->landmark_quality, 8 * nl);
-    if (A->landmark_use) put(o_use, A->landmark_use, nl);
-    if (nl) put(o_ob, A->obs_begin, 4 * (nl + 1));
-    put(o_op, A->obs_pose, 4 * no);
-    put(o_oc, A->obs_camera, 4 * no);
-    put(o_od, A->obs_descriptor, 48 * no);
-    put(o_or, A->obs_ray, 24 * no);
-    put(o_jc, A->job_camera, 4 * nj);
-    put(o_jp, A->job_pose_prepare, 56 * nj);
-    put(o_jm, A->job_pose_match, 56 * nj);
-    {  // the keypoints of the pass-0 jobs, then those of the pass-1 jobs; the job of every keypoint
-      int32_t* list = reinterpret_cast<int32_t*>(host + o_kl);
-      int32_t* job = reinterpret_cast<int32_t*>(host + o_kj);
-      size_t at0 = 0, at1 = nk0;
-      for (size_t j = 0; j < nj; ++j)
-        for (int32_t k = A->kp_begin[j]; k < A->kp_begin[j + 1]; ++k) {
-          job[k] = (int32_t)j;
-          list[A->job_pass[j] == 0 ? at0++ : at1++] = k;
-        }
-    }
-    put(o_kxy, A->keypoint, 16 * nk);
-    put(o_kd, A->descriptor, 48 * nk);
-    put(o_kr, A->ray, 24 * nk);
-    put(o_kv, A->ray_valid, nk);
-    put(o_klm, A->landmark, 4 * nk);
-    HIPCHK(hipMemcpyAsync(dev, host, upEnd, hipMemcpyHostToDevice, c->stream));
-    MatchDev D{};
-    D.n_jobs = A->n_jobs;
-    D.n_lm = A->n_landmarks;
-    D.n_kp0 = (int32_t)nk0;
-    D.n_kp1 = (int32_t)(nk - nk0);
-    D.imu_use = A->imu_use ? 1 : 0;
-    D.loop_closure = A->loop_closure ? 1 : 0;
-    D.threshold = A->matching_threshold;
-    auto at = [&](size_t off) { return dev + off; };
-    D.poses = reinterpret_cast<const double*>(at(o_pose));
-    D.cam = reinterpret_cast<const double*>(at(o_cam));
-    D.extr = reinterpret_cast<const double*>(at(o_ext));
-    D.lm = reinterpret_cast<const double*>(at(o_lm));
-    D.lm_quality = reinterpret_cast<const double*>(at(o_q));
-    D.lm_use = A->landmark_use ? reinterpret_cast<const uint8_t*>(at(o_use)) : nullptr;
-    D.obs_begin = reinterpret_cast<const int32_t*>(at(o_ob));
-    D.obs_pose = reinterpret_cast<const int32_t*>(at(o_op));
-    D.obs_cam = reinterpret_cast<const int32_t*>(at(o_oc));
-    D.obs_desc = reinterpret_cast<const uint32_t*>(at(o_od));
-    D.obs_ray = reinterpret_cast<const double*>(at(o_or));
-    D.job_cam = reinterpret_cast<const int32_t*>(at(o_jc));
-    D.job_pose_prepare = reinterpret_cast<const double*>(at(o_jp));
-    D.job_pose_match = reinterpret_cast<const double*>(at(o_jm));
-    D.kp_list = reinterpret_cast<const int32_t*>(at(o_kl));
-    D.kp_job = reinterpret_cast<const int32_t*>(at(o_kj));
-    D.kp_xy = reinterpret_cast<const double*>(at(o_kxy));
-    D.kp_desc = reinterpret_cast<const uint32_t*>(at(o_kd));
-    D.kp_ray = reinterpret_cast<const double*>(at(o_kr));
-    D.kp_ray_valid = reinterpret_cast<const uint8_t*>(at(o_kv));
-    D.kp_lm = reinterpret_cast<const int32_t*>(at(o_klm));
-    D.cand_n = reinterpret_cast<int32_t*>(at(o_cn));
-    D.cand_is3d = reinterpret_cast<uint8_t*>(at(o_c3));
-    D.cand_obs = reinterpret_cast<int32_t*>(at(o_co));
-    D.cand_proj = reinterpret_cast<double*>(at(o_cp));
-    D.cand_geo = reinterpret_cast<double*>(at(o_geo));
-    D.cand_desc = reinterpret_cast<uint32_t*>(at(o_desc));
-    D.out_match = reinterpret_cast<int32_t*>(at(o_m));
-    D.out_dist = reinterpret_cast<int32_t*>(at(o_d));
-    D.out_records = reinterpret_cast<int32_t*>(at(o_r));
-    D.out_sum = reinterpret_cast<double*>(at(o_s));
-    D.out_point = reinterpret_cast<double*>(at(o_pt));
-    launch_match_prepare(D, c->stream);
-    HIPCHK(hipGetLastError());
-    launch_match(D, c->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host + downBegin, dev + downBegin, downEnd - downBegin, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    auto get = [&](void* dst, size_t off, size_t bytes) {
-      if (dst && bytes) std::memcpy(dst, host + off, bytes);
-    };
-    get(R->cand_n, o_cn, 4 * njl);
-    get(R->cand_is3d, o_c3, njl);
-    get(R->cand_obs, o_co, 12 * njl);
-    get(R->cand_projection, o_cp, 16 * njl);
-    get(R->match_landmark, o_m, 4 * nk);
-    get(R->match_distance, o_d, 4 * nk);
-    get(R->n_records, o_r, 4 * nk);
-    get(R->record_repr_sum, o_s, 8 * nk);
-    get(R->point, o_pt, 32 * nk);
-    return (int)OKVISGPU_OK;
-  });
-}
-
-int okvisgpu_match_frames(okvisgpu_ctx* c, const okvisgpu_frame_match_batch* A, okvisgpu_frame_match_result* R) {
-  if (!c || !A || !R) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_frames: bad arguments");
-  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_frames: call after solve_end");
-  if (A->n_jobs < 0 || A->n_cameras < 0) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_frames: negative count");
-  if (A->n_jobs == 0) return OKVISGPU_OK;
-  return guarded(c, [&]() {
-    const std::string who = "match_frames: ";
-    const size_t nj = (size_t)A->n_jobs, nc = (size_t)A->n_cameras;
-    if (!A->job_mode || !A->job_camera0 || !A->job_camera1 || !A->job_pose0 || !A->job_pose1 || !A->job_extrinsics0 ||
-        !A->job_extrinsics1 || !A->kp0_begin || !A->kp1_begin)
-      throw ArgError{who + "job arrays missing"};
-    if (!nc || !A->cameras) throw ArgError{who + "cameras missing"};
-    if (A->kp0_begin[0] != 0) throw ArgError{who + "kp0_begin must start at 0"};
-    if (A->kp1_begin[0] != 0) throw ArgError{who + "kp1_begin must start at 0"};
-    for (size_t j = 0; j < nj; ++j) {
-      if (A->kp0_begin[j + 1] < A->kp0_begin[j]) throw ArgError{who + "kp0_begin not monotone at job " + std::to_string(j)};
-      if (A->kp1_begin[j + 1] < A->kp1_begin[j]) throw ArgError{who + "kp1_begin not monotone at job " + std::to_string(j)};
-    }
-    const size_t n0 = (size_t)A->kp0_begin[nj], n1 = (size_t)A->kp1_begin[nj];
-    if (n0 && (!A->size0 || !A->descriptor0 || !A->ray0 || !A->ray_valid0)) throw ArgError{who + "side-0 keypoint arrays missing"};
-    if (n1 && (!A->keypoint1 || !A->size1 || !A->descriptor1 || !A->ray1 || !A->ray_valid1))
-      throw ArgError{who + "side-1 keypoint arrays missing"};
-    for (size_t j = 0; j < nj; ++j) {
-      if (A->job_mode[j] != 0 && A->job_mode[j] != 1) throw ArgError{who + "job_mode not 0 / 1 at job " + std::to_string(j)};
-      if (A->job_camera0[j] < 0 || A->job_camera0[j] >= A->n_cameras)
-        throw ArgError{who + "job_camera0 out of range at job " + std::to_string(j)};
-      if (A->job_camera1[j] < 0 || A->job_camera1[j] >= A->n_cameras)
-        throw ArgError{who + "job_camera1 out of range at job " + std::to_string(j)};
-    }
-    std::vector<double> cam((size_t)kMatchCamDoubles * nc);
-    for (size_t k = 0; k < nc; ++k) {
-      const okvisgpu_camera& q = A->cameras[k];
-      if (q.distortion < 0 || q.distortion > 3) throw ArgError{who + "unknown distortion model of camera " + std::to_string(k)};
-      const double cv[kMatchCamDoubles] = {(double)q.distortion, q.fu, q.fv, q.cu, q.cv, q.dist[0], q.dist[1], q.dist[2],
-                                           q.dist[3], q.dist[4], q.dist[5], q.dist[6], q.dist[7], (double)q.width,
-                                           (double)q.height};
-      std::memcpy(&cam[kMatchCamDoubles * k], cv, sizeof(cv));
-    }
-    // the side-0 keypoints that take part (use0 and ray_valid0: in mode 1 a keypoint without a valid ray
-    // has no admissible candidate), per mode
-    size_t nl[2] = {0, 0};
-    for (size_t j = 0; j < nj; ++j)
-      for (int32_t k = A->kp0_begin[j]; k < A->kp0_begin[j + 1]; ++k)
-        if ((!A->use0 || A->use0[k]) && A->ray_valid0[k]) ++nl[A->job_mode[j]];
-    HIPCHK(hipSetDevice(c->device));
-    // device and pinned staging share one layout: uploaded [0, upEnd), read back [downBegin, downEnd),
-    // then what only the device holds
-    Arena M;
-    const size_t o_cam = M.reserve(8 * cam.size()), o_c0 = M.reserve(4 * nj), o_c1 = M.reserve(4 * nj),
-                 o_p0 = M.reserve(56 * nj), o_p1 = M.reserve(56 * nj), o_x0 = M.reserve(56 * nj), o_x1 = M.reserve(56 * nj),
-                 o_b1 = M.reserve(4 * (nj + 1)), o_j0 = M.reserve(4 * n0), o_j1 = M.reserve(4 * n1),
-                 o_list = M.reserve(4 * (nl[0] + nl[1])), o_s0 = M.reserve(8 * n0), o_d0 = M.reserve(48 * n0),
-                 o_r0 = M.reserve(24 * n0), o_xy1 = M.reserve(16 * n1), o_s1 = M.reserve(8 * n1), o_d1 = M.reserve(48 * n1),
-                 o_r1 = M.reserve(24 * n1), o_v1 = M.reserve(n1), o_u1 = M.reserve(n1);
-    const size_t upEnd = M.size;
-    const size_t o_m = M.reserve(4 * n0), downBegin = o_m, o_d = M.reserve(4 * n0), o_pt = M.reserve(32 * n0),
-                 o_q = M.reserve(8 * n0), o_i = M.reserve(n0);
-    const size_t downEnd = M.size;
-    const size_t o_geo = M.reserve(8 * kFrameGeoDoubles * nj), o_e0 = M.reserve(24 * n0), o_e1 = M.reserve(24 * n1),
-                 o_f1 = M.reserve(n1);
-    if (M.size > c->frameMatchScratchBytes) {
-      if (c->frameMatchScratch) HIPCHK(hipFree(c->frameMatchScratch));
-      c->frameMatchScratch = nullptr;
-      c->frameMatchScratchBytes = 0;
-      HIPCHK(hipMalloc(&c->frameMatchScratch, M.size));
-      c->frameMatchScratchBytes = M.size;
-    }
-    char* dev = static_cast<char*>(c->frameMatchScratch);
-    char* host = c->paramStage(downEnd);
-    auto put = [&](size_t off, const void* src, size_t bytes) {
-      if (bytes) std::memcpy(host + off, src, bytes);
-    };
-    put(o_cam, cam.data(), 8 * cam.size());
-    put(o_c0, A->job_camera0, 4 * nj);
-    put(o_c1, A->job_camera1, 4 * nj);
-    put(o_p0, A->job_pose0, 56 * nj);
-    put(o_p1, A->job_pose1, 56 * nj);
-    put(o_x0, A->job_extrinsics0, 56 * nj);
-    put(o_x1, A->job_extrinsics1, 56 * nj);
-    put(o_b1, A->kp1_begin, 4 * (nj + 1));
-    {  // the job of every keypoint; the participating side-0 keypoints of the mode-0 jobs, then the mode-1 jobs'
-      int32_t* job0 = reinterpret_cast<int32_t*>(host + o_j0);
-      int32_t* job1 = reinterpret_cast<int32_t*>(host + o_j1);
-      int32_t* list = reinterpret_cast<int32_t*>(host + o_list);
-      size_t at[2] = {0, nl[0]};
-      for (size_t j = 0; j < nj; ++j) {
-        for (int32_t k = A->kp0_begin[j]; k < A->kp0_begin[j + 1]; ++k) {
-          job0[k] = (int32_t)j;
-          if ((!A->use0 || A->use0[k]) && A->ray_valid0[k]) list[at[A->job_mode[j]]++] = k;
-        }
-        for (int32_t k = A->kp1_begin[j]; k < A->kp1_begin[j + 1]; ++k) job1[k] = (int32_t)j;
-      }
-    }
-    put(o_s0, A->size0, 8 * n0);
-    put(o_d0, A->descriptor0, 48 * n0);
-    put(o_r0, A->ray0, 24 * n0);
-    put(o_xy1, A->keypoint1, 16 * n1);
-    put(o_s1, A->size1, 8 * n1);
-    put(o_d1, A->descriptor1, 48 * n1);
-    put(o_r1, A->ray1, 24 * n1);
-    put(o_v1, A->ray_valid1, n1);
-    if (A->use1) put(o_u1, A->use1, n1);
-    HIPCHK(hipMemcpyAsync(dev, host, upEnd, hipMemcpyHostToDevice, c->stream));
-    FrameMatchDev D{};
-    D.n_jobs = A->n_jobs;
-    D.n_kp0 = (int32_t)n0;
-    D.n_kp1 = (int32_t)n1;
-    D.n_list0 = (int32_t)nl[0];
-    D.n_list1 = (int32_t)nl[1];
-    {  // d < best as the reference starts it: uint32_t(threshold) in mode 0, the double itself in mode 1
-      const double t = A->matching_threshold;
-      const double lim = 385.0;  // above every distance of 384 bits
-      D.best_init[0] = !(t > 0.0) ? 0 : (int32_t)std::floor(std::min(t, lim));
-      D.best_init[1] = !(t > 0.0) ? 0 : (int32_t)std::ceil(std::min(t, lim));
-    }
-    auto at = [&](size_t off) { return dev + off; };
-    D.cam = reinterpret_cast<const double*>(at(o_cam));
-    D.job_cam0 = reinterpret_cast<const int32_t*>(at(o_c0));
-    D.job_cam1 = reinterpret_cast<const int32_t*>(at(o_c1));
-    D.job_pose0 = reinterpret_cast<const double*>(at(o_p0));
-    D.job_pose1 = reinterpret_cast<const double*>(at(o_p1));
-    D.job_ext0 = reinterpret_cast<const double*>(at(o_x0));
-    D.job_ext1 = reinterpret_cast<const double*>(at(o_x1));
-    D.kp1_begin = reinterpret_cast<const int32_t*>(at(o_b1));
-    D.kp0_job = reinterpret_cast<const int32_t*>(at(o_j0));
-    D.kp1_job = reinterpret_cast<const int32_t*>(at(o_j1));
-    D.kp_list = reinterpret_cast<const int32_t*>(at(o_list));
-    D.size0 = reinterpret_cast<const double*>(at(o_s0));
-    D.desc0 = reinterpret_cast<const uint32_t*>(at(o_d0));
-    D.ray0 = reinterpret_cast<const double*>(at(o_r0));
-    D.xy1 = reinterpret_cast<const double*>(at(o_xy1));
-    D.size1 = reinterpret_cast<const double*>(at(o_s1));
-    D.desc1 = reinterpret_cast<const uint32_t*>(at(o_d1));
-    D.ray1 = reinterpret_cast<const double*>(at(o_r1));
-    D.valid1 = reinterpret_cast<const uint8_t*>(at(o_v1));
-    D.use1 = A->use1 ? reinterpret_cast<const uint8_t*>(at(o_u1)) : nullptr;
-    D.job_geo = reinterpret_cast<double*>(at(o_geo));
-    D.e0 = reinterpret_cast<double*>(at(o_e0));
-    D.e1 = reinterpret_cast<double*>(at(o_e1));
-    D.flag1 = reinterpret_cast<uint8_t*>(at(o_f1));
-    D.out_match = reinterpret_cast<int32_t*>(at(o_m));
-    D.out_dist = reinterpret_cast<int32_t*>(at(o_d));
-    D.out_point = reinterpret_cast<double*>(at(o_pt));
-    D.out_quality = reinterpret_cast<double*>(at(o_q));
-    D.out_init = reinterpret_cast<uint8_t*>(at(o_i));
-    launch_match_frames_prepare(D, c->stream);
-    HIPCHK(hipGetLastError());
-    launch_match_frames(D, c->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host + downBegin, dev + downBegin, downEnd - downBegin, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    auto get = [&](void* dst, size_t off, size_t bytes) {
-      if (dst && bytes) std::memcpy(dst, host + off, bytes);
-    };
-    get(R->match, o_m, 4 * n0);
-    get(R->distance, o_d, 4 * n0);
-    get(R->point, o_pt, 32 * n0);
-    get(R->quality, o_q, 8 * n0);
-    get(R->initialisable, o_i, n0);
-    return (int)OKVISGPU_OK;
-  });
-}
-
-int okvisgpu_place_match(okvisgpu_ctx* c, const okvisgpu_place_match_batch* A, okvisgpu_place_match_result* R) {
-  if (!c || !A || !R) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_match: bad arguments");
-  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_match: call after solve_end");
-  if (A->n_jobs < 0 || A->n_cameras < 0 || A->n_images < 0)
-    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_match: negative count");
-  if (A->n_jobs == 0) return OKVISGPU_OK;
-  return guarded(c, [&]() {
-    const std::string who = "place_match: ";
-    const size_t nj = (size_t)A->n_jobs, nc = (size_t)A->n_cameras, ni = (size_t)A->n_images;
-    if (!A->lm_begin || (nc && !A->job_image)) throw ArgError{who + "job arrays missing"};
-    if (ni && !A->kp_begin) throw ArgError{who + "kp_begin missing"};
-    if (ni && A->kp_begin[0] != 0) throw ArgError{who + "kp_begin must start at 0"};
-    for (size_t i = 0; i < ni; ++i)
-      if (A->kp_begin[i + 1] < A->kp_begin[i]) throw ArgError{who + "kp_begin not monotone at image " + std::to_string(i)};
-    const size_t nk = ni ? (size_t)A->kp_begin[ni] : 0;
-    if (nk && !A->descriptor) throw ArgError{who + "descriptor missing"};
-    if (A->lm_begin[0] != 0) throw ArgError{who + "lm_begin must start at 0"};
-    for (size_t j = 0; j < nj; ++j)
-      if (A->lm_begin[j + 1] < A->lm_begin[j]) throw ArgError{who + "lm_begin not monotone at job " + std::to_string(j)};
-    const size_t nl = (size_t)A->lm_begin[nj];
-    if (nl && !A->desc_begin) throw ArgError{who + "desc_begin missing"};
-    if (nl && A->desc_begin[0] != 0) throw ArgError{who + "desc_begin must start at 0"};
-    for (size_t l = 0; l < nl; ++l)
-      if (A->desc_begin[l + 1] < A->desc_begin[l])
-        throw ArgError{who + "desc_begin not monotone at landmark " + std::to_string(l)};
-    const size_t nd = nl ? (size_t)A->desc_begin[nl] : 0;
-    if (nd && !A->old_descriptor) throw ArgError{who + "old_descriptor missing"};
-    for (size_t i = 0; i < nj * nc; ++i)
-      if (A->job_image[i] < -1 || A->job_image[i] >= A->n_images)
-        throw ArgError{who + "job_image out of range at job " + std::to_string(i / nc)};
-    if (nl * nc > (size_t)0x7fffffff) throw ArgError{who + "too many (landmark, camera) pairs"};
-    const size_t no = nl * nc;
-    if (!no) {  // nothing to match: every job has ctr = 0
-      if (R->job_matches) std::fill(R->job_matches, R->job_matches + nj, 0);
-      return (int)OKVISGPU_OK;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    // device and pinned staging share one layout: uploaded [0, upEnd), read back [downBegin, downEnd)
-    Arena M;
-    const size_t o_kb = M.reserve(4 * (ni + 1)), o_d = M.reserve(48 * nk), o_ji = M.reserve(4 * nj * nc),
-                 o_lj = M.reserve(4 * nl), o_db = M.reserve(4 * (nl + 1)), o_od = M.reserve(48 * nd);
-    const size_t upEnd = M.size;
-    const size_t o_k = M.reserve(4 * no), downBegin = o_k, o_dist = M.reserve(4 * no);
-    const size_t downEnd = M.size;
-    if (M.size > c->placeScratchBytes) {
-      if (c->placeScratch) HIPCHK(hipFree(c->placeScratch));
-      c->placeScratch = nullptr;
-      c->placeScratchBytes = 0;
-      HIPCHK(hipMalloc(&c->placeScratch, M.size));
-      c->placeScratchBytes = M.size;
-    }
-    char* dev = static_cast<char*>(c->placeScratch);
-    char* host = c->paramStage(downEnd);
-    auto put = [&](size_t off, const void* src, size_t bytes) {
-      if (bytes) std::memcpy(host + off, src, bytes);
-    };
-    if (ni) put(o_kb, A->kp_begin, 4 * (ni + 1));
-    else std::memset(host + o_kb, 0, 4);
-    put(o_d, A->descriptor, 48 * nk);
-    put(o_ji, A->job_image, 4 * nj * nc);
-    {  // the job of every landmark
-      int32_t* lj = reinterpret_cast<int32_t*>(host + o_lj);
-      for (size_t j = 0; j < nj; ++j)
-        for (int32_t l = A->lm_begin[j]; l < A->lm_begin[j + 1]; ++l) lj[l] = (int32_t)j;
-    }
-    put(o_db, A->desc_begin, 4 * (nl + 1));
-    put(o_od, A->old_descriptor, 48 * nd);
-    HIPCHK(hipMemcpyAsync(dev, host, upEnd, hipMemcpyHostToDevice, c->stream));
-    PlaceMatchDev D{};
-    D.n_lm = (int32_t)nl;
-    D.n_cam = (int32_t)nc;
-    {  // distMin's start: uint32_t(threshold), above no distance of 384 bits when clamped to 385
-      const double t = A->matching_threshold;
-      D.best_init = !(t > 0.0) ? 0 : (int32_t)std::floor(std::min(t, 385.0));
-      D.start_matches = (double)D.best_init < t && t <= 385.0;  // (:338 on a distMin nothing replaced)
-    }
-    D.kp_begin = reinterpret_cast<const int32_t*>(dev + o_kb);
-    D.desc = reinterpret_cast<const uint32_t*>(dev + o_d);
-    D.job_image = reinterpret_cast<const int32_t*>(dev + o_ji);
-    D.lm_job = reinterpret_cast<const int32_t*>(dev + o_lj);
-    D.desc_begin = reinterpret_cast<const int32_t*>(dev + o_db);
-    D.old_desc = reinterpret_cast<const uint32_t*>(dev + o_od);
-    D.out_kp = reinterpret_cast<int32_t*>(dev + o_k);
-    D.out_dist = reinterpret_cast<int32_t*>(dev + o_dist);
-    launch_place_match(D, c->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host + downBegin, dev + downBegin, downEnd - downBegin, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (R->match_keypoint) std::memcpy(R->match_keypoint, host + o_k, 4 * no);
-    if (R->match_distance) std::memcpy(R->match_distance, host + o_dist, 4 * no);
-    if (R->job_matches) {  // ctr: the job's (landmark, camera) pairs with a match
-      const int32_t* mk = reinterpret_cast<const int32_t*>(host + o_k);
-      for (size_t j = 0; j < nj; ++j) {
-        int32_t ctr = 0;
-        for (size_t i = (size_t)A->lm_begin[j] * nc; i < (size_t)A->lm_begin[j + 1] * nc; ++i) ctr += mk[i] >= 0;
-        R->job_matches[j] = ctr;
-      }
-    }
-    return (int)OKVISGPU_OK;
-  });
-}
-
-int okvisgpu_place_refine(okvisgpu_ctx* c, const okvisgpu_place_refine_batch* A, okvisgpu_place_refine_result* R) {
-  if (!c || !A || !R) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_refine: bad arguments");
-  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_refine: call after solve_end");
-  if (A->n_jobs < 0 || A->n_cameras < 0 || A->max_num_iterations < 0)
-    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_refine: negative count");
-  if (A->loss.kind < OKVISGPU_LOSS_NONE || A->loss.kind > OKVISGPU_LOSS_TOLERANT)
-    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_refine: unknown loss kind " + std::to_string(A->loss.kind));
-  if (!lossValid(A->loss)) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "place_refine: non-positive loss scale");
-  if (A->n_jobs == 0) return OKVISGPU_OK;
-  return guarded(c, [&]() {
-    const std::string who = "place_refine: ";
-    const size_t nj = (size_t)A->n_jobs, nc = (size_t)A->n_cameras;
-    if (!A->pose || !A->obs_begin) throw ArgError{who + "job arrays missing"};
-    if (A->obs_begin[0] != 0) throw ArgError{who + "obs_begin must start at 0"};
-    for (size_t j = 0; j < nj; ++j)
-      if (A->obs_begin[j + 1] < A->obs_begin[j]) throw ArgError{who + "obs_begin not monotone at job " + std::to_string(j)};
-    const size_t no = (size_t)A->obs_begin[nj];
-    if (no && (!A->obs_camera || !A->obs_keypoint || !A->obs_sqrt_info || !A->obs_point))
-      throw ArgError{who + "observation arrays missing"};
-    if (no && (!nc || !A->cameras || !A->extrinsics)) throw ArgError{who + "cameras missing"};
-    for (size_t o = 0; o < no; ++o)
-      if (A->obs_camera[o] < 0 || A->obs_camera[o] >= A->n_cameras)
-        throw ArgError{who + "obs_camera out of range at observation " + std::to_string(o)};
-    std::vector<double> cam((size_t)kCamDoubles * nc);
-    for (size_t k = 0; k < nc && A->cameras; ++k) {
-      const okvisgpu_camera& q = A->cameras[k];
-      if (q.distortion < 0 || q.distortion > 3) throw ArgError{who + "unknown distortion model of camera " + std::to_string(k)};
-      const double cv[kCamDoubles] = {(double)q.distortion, q.fu, q.fv, q.cu, q.cv, q.dist[0], q.dist[1], q.dist[2],
-                                      q.dist[3], q.dist[4], q.dist[5], q.dist[6], q.dist[7]};
-      std::memcpy(&cam[kCamDoubles * k], cv, sizeof(cv));
-    }
-    HIPCHK(hipSetDevice(c->device));
-    // device and pinned staging share one layout: uploaded [0, upEnd), read back [downBegin, downEnd);
-    // the poses are both
-    Arena M;
-    const size_t o_cam = M.reserve(8 * cam.size()), o_ex = M.reserve(56 * nc), o_ob = M.reserve(4 * (nj + 1)),
-                 o_oc = M.reserve(4 * no), o_kp = M.reserve(16 * no), o_L = M.reserve(32 * no), o_pt = M.reserve(32 * no);
-    const size_t o_pose = M.reserve(56 * nj), downBegin = o_pose;
-    const size_t upEnd = M.size;
-    const size_t o_real = M.reserve(8 * kPlaceReal * nj), o_int = M.reserve(4 * kPlaceInt * nj);
-    const size_t downEnd = M.size;
-    if (M.size > c->placeScratchBytes) {
-      if (c->placeScratch) HIPCHK(hipFree(c->placeScratch));
-      c->placeScratch = nullptr;
-      c->placeScratchBytes = 0;
-      HIPCHK(hipMalloc(&c->placeScratch, M.size));
-      c->placeScratchBytes = M.size;
-    }
-    char* dev = static_cast<char*>(c->placeScratch);
-    char* host = c->paramStage(downEnd);
-    auto put = [&](size_t off, const void* src, size_t bytes) {
-      if (bytes) std::memcpy(host + off, src, bytes);
-    };
-    put(o_cam, cam.data(), 8 * cam.size());
-    if (A->extrinsics) put(o_ex, A->extrinsics, 56 * nc);
-    put(o_ob, A->obs_begin, 4 * (nj + 1));
-    put(o_oc, A->obs_camera, 4 * no);
-    put(o_kp, A->obs_keypoint, 16 * no);
-    put(o_L, A->obs_sqrt_info, 32 * no);
-    put(o_pt, A->obs_point, 32 * no);
-    put(o_pose, A->pose, 56 * nj);
-    HIPCHK(hipMemcpyAsync(dev, host, upEnd, hipMemcpyHostToDevice, c->stream));
-    PlaceRefineDev D{};
-    D.n_jobs = A->n_jobs;
-    D.max_iter = A->max_num_iterations;
-    D.loss_kind = A->loss.kind;
-    D.loss_a = A->loss.a;
-    D.loss_b = A->loss.b;
-    D.cam = reinterpret_cast<const double*>(dev + o_cam);
-    D.extr = reinterpret_cast<const double*>(dev + o_ex);
-    D.obs_begin = reinterpret_cast<const int32_t*>(dev + o_ob);
-    D.obs_cam = reinterpret_cast<const int32_t*>(dev + o_oc);
-    D.obs_kp = reinterpret_cast<const double*>(dev + o_kp);
-    D.obs_L = reinterpret_cast<const double*>(dev + o_L);
-    D.obs_pt = reinterpret_cast<const double*>(dev + o_pt);
-    D.pose = reinterpret_cast<double*>(dev + o_pose);
-    D.out_real = reinterpret_cast<double*>(dev + o_real);
-    D.out_int = reinterpret_cast<int32_t*>(dev + o_int);
-    launch_place_refine(D, c->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host + downBegin, dev + downBegin, downEnd - downBegin, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const double* real = reinterpret_cast<const double*>(host + o_real);
-    const int32_t* in = reinterpret_cast<const int32_t*>(host + o_int);
-    for (size_t j = 0; j < nj; ++j) {
-      if (A->obs_begin[j + 1] > A->obs_begin[j]) std::memcpy(A->pose + 7 * j, host + o_pose + 56 * j, 56);
-      const double* r = real + kPlaceReal * j;
-      const int32_t* q = in + kPlaceInt * j;
-      if (R->initial_cost) R->initial_cost[j] = r[0];
-      if (R->final_cost) R->final_cost[j] = r[1];
-      if (R->H) std::memcpy(R->H + 36 * j, r + 2, 36 * sizeof(double));
-      if (R->num_iterations) R->num_iterations[j] = q[0];
-      if (R->num_successful_steps) R->num_successful_steps[j] = q[1];
-      if (R->num_unsuccessful_steps) R->num_unsuccessful_steps[j] = q[2];
-      if (R->termination_type) R->termination_type[j] = q[3];
-      if (R->n_outliers) R->n_outliers[j] = q[4];
-    }
-    return (int)OKVISGPU_OK;
-  });
-}
-
 int okvisgpu_update_landmarks(okvisgpu_ctx* c, okvisgpu_landmark_update* updates) {
   if (!c || !updates) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "update_landmarks: bad arguments");
   if (!c->haveProblem) return fail(c, OKVISGPU_ERR_NO_PROBLEM, "no problem set");
@@ -2502,246 +1610,6 @@ int okvisgpu_covisibilities(okvisgpu_ctx* c, okvisgpu_covisibility* out) {
   return guarded(c, [&]() {
     HIPCHK(hipSetDevice(c->device));
     c->covisibilities(out);
-    return (int)OKVISGPU_OK;
-  });
-}
-
-// An okvisgpu_twopose_edges batch checked and uploaded (okvisgpu_twopose_compute and
-// okvisgpu_twopose_extrinsics_compute): one device allocation for the inputs and for whatever `more`
-// reserves after them; T.out stays null. Throws ArgError with `who` in front.
-struct TwoPoseUpload {
-  std::unique_ptr<char, void (*)(char*)> mem{nullptr, [](char* p) { (void)hipFree(p); }};
-  TwoPoseDev T{};
-  int nl = 0, no = 0;
-};
-static void uploadTwoPose(okvisgpu_ctx* c, const okvisgpu_twopose_edges* E, const std::string& who, TwoPoseUpload& U,
-                          const std::function<void(Arena&, int, int)>& more) {
-  const int ne = E->n_edges;
-  const int nl = E->landmark_begin[ne] - E->landmark_begin[0];
-  if (E->landmark_begin[0] != 0 || nl < 0) throw ArgError{who + ": landmark_begin must start at 0"};
-  for (int e = 0; e < ne; ++e)
-    if (E->landmark_begin[e + 1] < E->landmark_begin[e]) throw ArgError{who + ": landmark_begin not monotone"};
-  const int no = nl ? E->obs_begin[nl] - E->obs_begin[0] : 0;
-  if (nl && (E->obs_begin[0] != 0 || no < 0)) throw ArgError{who + ": obs_begin must start at 0"};
-  for (int l = 0; l < nl; ++l)
-    if (E->obs_begin[l + 1] < E->obs_begin[l]) throw ArgError{who + ": obs_begin not monotone"};
-  if (no && (!E->landmarks || !E->obs_other || !E->obs_camera || !E->obs_keypoint || !E->obs_sqrt_info ||
-             !E->cameras || !E->extrinsics))
-    throw ArgError{who + ": observation arrays missing"};
-  for (int o = 0; o < no; ++o)
-    if (E->obs_camera[o] < 0 || E->obs_camera[o] >= E->n_cameras) throw ArgError{who + ": obs_camera out of range"};
-  std::vector<double> cam((size_t)kCamDoubles * std::max(1, E->n_cameras));
-  for (int k = 0; k < E->n_cameras; ++k) {
-    const okvisgpu_camera& q = E->cameras[k];
-    if (q.distortion < 0 || q.distortion > 3) throw ArgError{who + ": unknown distortion model"};
-    const double cv[kCamDoubles] = {(double)q.distortion, q.fu, q.fv, q.cu, q.cv, q.dist[0], q.dist[1],
-                                    q.dist[2], q.dist[3], q.dist[4], q.dist[5], q.dist[6], q.dist[7]};
-    std::memcpy(&cam[kCamDoubles * (size_t)k], cv, sizeof(cv));
-  }
-  std::vector<uint8_t> cauchy(std::max(1, no), 1);
-  if (E->obs_cauchy) for (int o = 0; o < no; ++o) cauchy[o] = E->obs_cauchy[o] ? 1 : 0;
-  // one scratch allocation for inputs and outputs
-  Arena A;
-  auto put = [&](size_t bytes) { return A.reserve(bytes); };
-  const size_t o_ref = put(56 * (size_t)ne), o_oth = put(56 * (size_t)ne), o_cam = put(cam.size() * 8),
-               o_ex = put(56 * (size_t)std::max(1, E->n_cameras)), o_lb = put(4 * (size_t)(ne + 1)),
-               o_lm = put(32 * (size_t)std::max(1, nl)), o_ob = put(4 * (size_t)(nl + 1)),
-               o_oo = put((size_t)std::max(1, no)), o_oc = put(4 * (size_t)std::max(1, no)),
-               o_kp = put(16 * (size_t)std::max(1, no)), o_L = put(32 * (size_t)std::max(1, no)),
-               o_ca = put((size_t)std::max(1, no));
-  more(A, nl, no);
-  char* base = nullptr;
-  HIPCHK(hipMalloc(&base, A.size));
-  U.mem.reset(base);
-  auto up = [&](size_t off, const void* src, size_t bytes) {
-    if (bytes && src) HIPCHK(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, c->stream));
-  };
-  up(o_ref, E->ref_pose, 56 * (size_t)ne);
-  up(o_oth, E->other_pose, 56 * (size_t)ne);
-  up(o_cam, cam.data(), cam.size() * 8);
-  up(o_ex, E->extrinsics, 56 * (size_t)E->n_cameras);
-  up(o_lb, E->landmark_begin, 4 * (size_t)(ne + 1));
-  if (nl) {
-    up(o_lm, E->landmarks, 32 * (size_t)nl);
-    up(o_ob, E->obs_begin, 4 * (size_t)(nl + 1));
-  }
-  if (no) {
-    up(o_oo, E->obs_other, (size_t)no);
-    up(o_oc, E->obs_camera, 4 * (size_t)no);
-    up(o_kp, E->obs_keypoint, 16 * (size_t)no);
-    up(o_L, E->obs_sqrt_info, 32 * (size_t)no);
-    up(o_ca, cauchy.data(), (size_t)no);
-  }
-  TwoPoseDev& T = U.T;
-  T.n_edges = ne;
-  T.n_cam = E->n_cameras;
-  T.ref_pose = reinterpret_cast<const double*>(base + o_ref);
-  T.other_pose = reinterpret_cast<const double*>(base + o_oth);
-  T.cam = reinterpret_cast<const double*>(base + o_cam);
-  T.extr = reinterpret_cast<const double*>(base + o_ex);
-  T.lm_begin = reinterpret_cast<const int32_t*>(base + o_lb);
-  T.lm = reinterpret_cast<const double*>(base + o_lm);
-  T.obs_begin = reinterpret_cast<const int32_t*>(base + o_ob);
-  T.obs_other = reinterpret_cast<const uint8_t*>(base + o_oo);
-  T.obs_cam = reinterpret_cast<const int32_t*>(base + o_oc);
-  T.obs_kp = reinterpret_cast<const double*>(base + o_kp);
-  T.obs_L = reinterpret_cast<const double*>(base + o_L);
-  T.obs_cauchy = reinterpret_cast<const uint8_t*>(base + o_ca);
-  if (!nl) HIPCHK(hipMemsetAsync(base + o_ob, 0, 4, c->stream));
-  U.nl = nl;
-  U.no = no;
-}
-
-int okvisgpu_twopose_compute(okvisgpu_ctx* c, const okvisgpu_twopose_edges* E, double* delta_x, double* sqrt_info,
-                             double* lin_point, double* H00, double* b0) {
-  if (!c || !E || E->n_edges < 0) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "twopose_compute: bad arguments");
-  if (E->n_edges == 0) return OKVISGPU_OK;
-  if (!E->ref_pose || !E->other_pose || !E->landmark_begin || !E->obs_begin || !delta_x || !sqrt_info || !lin_point)
-    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "twopose_compute: missing arrays");
-  return guarded(c, [&]() {
-    HIPCHK(hipSetDevice(c->device));
-    const int ne = E->n_edges;
-    TwoPoseUpload U;
-    size_t o_out = 0;
-    uploadTwoPose(c, E, "twopose_compute", U, [&](Arena& A, int, int) { o_out = A.reserve(8 * (size_t)kTwoPoseOut * ne); });
-    TwoPoseDev& T = U.T;
-    T.out = reinterpret_cast<double*>(U.mem.get() + o_out);
-    launch_twopose_compute(T, c->stream);
-    HIPCHK(hipGetLastError());
-    std::vector<double> out((size_t)kTwoPoseOut * ne);
-    HIPCHK(hipMemcpyAsync(out.data(), T.out, out.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int e = 0; e < ne; ++e) {
-      const double* r = &out[(size_t)kTwoPoseOut * e];
-      std::memcpy(&delta_x[6 * (size_t)e], r, 6 * 8);
-      std::memcpy(&sqrt_info[36 * (size_t)e], r + 6, 36 * 8);
-      std::memcpy(&lin_point[7 * (size_t)e], r + 42, 7 * 8);
-      if (H00) std::memcpy(&H00[36 * (size_t)e], r + 49, 36 * 8);
-      if (b0) std::memcpy(&b0[6 * (size_t)e], r + 85, 6 * 8);
-    }
-    return (int)OKVISGPU_OK;
-  });
-}
-
-int okvisgpu_twopose_extrinsics_compute(okvisgpu_ctx* c, const okvisgpu_twopose_edges* E, double* delta_x,
-                                        double* sqrt_info, double* lin_point, uint8_t* camera_seen, double* H00,
-                                        double* b0) {
-  if (!c || !E || E->n_edges < 0 || E->n_cameras < 0)
-    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "twopose_extrinsics_compute: bad arguments");
-  static_assert(kTwoPoseMaxCam == OKVISGPU_TWOPOSE_MAX_CAMERAS, "device bound and header bound differ");
-  if (E->n_cameras > OKVISGPU_TWOPOSE_MAX_CAMERAS)
-    return fail(c, OKVISGPU_ERR_UNSUPPORTED, "twopose_extrinsics_compute: more than OKVISGPU_TWOPOSE_MAX_CAMERAS cameras");
-  if (E->n_edges == 0) return OKVISGPU_OK;
-  if (!E->ref_pose || !E->other_pose || !E->landmark_begin || !E->obs_begin || !delta_x || !sqrt_info || !lin_point ||
-      (E->n_cameras && !camera_seen))
-    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "twopose_extrinsics_compute: missing arrays");
-  return guarded(c, [&]() {
-    HIPCHK(hipSetDevice(c->device));
-    const size_t ne = (size_t)E->n_edges, nc = (size_t)E->n_cameras, D = 6 + 6 * nc;
-    TwoPoseUpload U;
-    // scratch records of pass 1 | outputs, zero-filled: the kernel writes the observed rows only
-    size_t o_rec = 0, o_flag = 0, o_lmr = 0, o_dx = 0, o_J = 0, o_lin = 0, o_H = 0, o_b = 0, o_seen = 0, outEnd = 0;
-    uploadTwoPose(c, E, "twopose_extrinsics_compute", U, [&](Arena& A, int nl, int no) {
-      o_rec = A.reserve(8 * (size_t)kTpxObsRec * std::max(1, no));
-      o_flag = A.reserve(4 * (size_t)std::max(1, no));
-      o_lmr = A.reserve(8 * (size_t)kTpxLmRec * std::max(1, nl));
-      o_dx = A.reserve(8 * D * ne);
-      o_J = A.reserve(8 * D * D * ne);
-      o_lin = A.reserve(56 * ne);
-      o_H = A.reserve(8 * D * D * ne);
-      o_b = A.reserve(8 * D * ne);
-      o_seen = A.reserve(std::max<size_t>(1, nc * ne));
-      outEnd = A.size;
-    });
-    char* base = U.mem.get();
-    TwoPoseExtrDev X{};
-    X.in = U.T;
-    X.obs_rec = reinterpret_cast<double*>(base + o_rec);
-    X.obs_flag = reinterpret_cast<int32_t*>(base + o_flag);
-    X.lm_rec = reinterpret_cast<double*>(base + o_lmr);
-    X.delta_x = reinterpret_cast<double*>(base + o_dx);
-    X.sqrt_info = reinterpret_cast<double*>(base + o_J);
-    X.lin_point = reinterpret_cast<double*>(base + o_lin);
-    X.H00 = reinterpret_cast<double*>(base + o_H);
-    X.b0 = reinterpret_cast<double*>(base + o_b);
-    X.seen = reinterpret_cast<uint8_t*>(base + o_seen);
-    HIPCHK(hipMemsetAsync(base + o_dx, 0, outEnd - o_dx, c->stream));
-    launch_twopose_extr_compute(X, c->stream);
-    HIPCHK(hipGetLastError());
-    std::vector<char> out(outEnd - o_dx);
-    HIPCHK(hipMemcpyAsync(out.data(), base + o_dx, out.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    auto down = [&](void* dst, size_t off, size_t bytes) {
-      if (dst && bytes) std::memcpy(dst, out.data() + (off - o_dx), bytes);
-    };
-    down(delta_x, o_dx, 8 * D * ne);
-    down(sqrt_info, o_J, 8 * D * D * ne);
-    down(lin_point, o_lin, 56 * ne);
-    down(H00, o_H, 8 * D * D * ne);
-    down(b0, o_b, 8 * D * ne);
-    down(camera_seen, o_seen, nc * ne);
-    return (int)OKVISGPU_OK;
-  });
-}
-
-int okvisgpu_twopose_extrinsics_evaluate(okvisgpu_ctx* c, const okvisgpu_twopose_extrinsics_eval* V, double* r,
-                                         double* J_ref, double* J_other, double* J_extrinsics) {
-  if (!c || !V || V->n_edges < 0 || V->n_cameras < 0)
-    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "twopose_extrinsics_evaluate: bad arguments");
-  if (V->n_cameras > OKVISGPU_TWOPOSE_MAX_CAMERAS)
-    return fail(c, OKVISGPU_ERR_UNSUPPORTED, "twopose_extrinsics_evaluate: more than OKVISGPU_TWOPOSE_MAX_CAMERAS cameras");
-  if (V->n_edges == 0) return OKVISGPU_OK;
-  if (!V->ref_pose || !V->other_pose || !V->delta_x || !V->sqrt_info || !V->lin_point ||
-      (V->n_cameras && (!V->extrinsics || !V->lin_extrinsics || !V->camera_seen)))
-    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "twopose_extrinsics_evaluate: missing arrays");
-  return guarded(c, [&]() {
-    HIPCHK(hipSetDevice(c->device));
-    const size_t ne = (size_t)V->n_edges, nc = (size_t)V->n_cameras, D = 6 + 6 * nc;
-    Arena A;
-    const size_t o_ref = A.reserve(56 * ne), o_oth = A.reserve(56 * ne), o_ex = A.reserve(56 * nc),
-                 o_dx = A.reserve(8 * D * ne), o_J = A.reserve(8 * D * D * ne), o_lin = A.reserve(56 * ne),
-                 o_lex = A.reserve(56 * nc * ne), o_seen = A.reserve(nc * ne);
-    const size_t o_r = r ? A.reserve(8 * D * ne) : 0, o_jr = J_ref ? A.reserve(48 * D * ne) : 0,
-                 o_jo = J_other ? A.reserve(48 * D * ne) : 0, o_je = J_extrinsics ? A.reserve(48 * D * nc * ne) : 0;
-    char* base = nullptr;
-    HIPCHK(hipMalloc(&base, A.size));
-    std::unique_ptr<char, void (*)(char*)> guard(base, [](char* p) { (void)hipFree(p); });
-    auto up = [&](size_t off, const void* src, size_t bytes) {
-      if (bytes && src) HIPCHK(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, c->stream));
-    };
-    up(o_ref, V->ref_pose, 56 * ne);
-    up(o_oth, V->other_pose, 56 * ne);
-    up(o_ex, V->extrinsics, 56 * nc);
-    up(o_dx, V->delta_x, 8 * D * ne);
-    up(o_J, V->sqrt_info, 8 * D * D * ne);
-    up(o_lin, V->lin_point, 56 * ne);
-    up(o_lex, V->lin_extrinsics, 56 * nc * ne);
-    up(o_seen, V->camera_seen, nc * ne);
-    TwoPoseExtrEvalDev T{};
-    T.n_edges = V->n_edges;
-    T.n_cam = V->n_cameras;
-    T.ref_pose = reinterpret_cast<const double*>(base + o_ref);
-    T.other_pose = reinterpret_cast<const double*>(base + o_oth);
-    T.extr = reinterpret_cast<const double*>(base + o_ex);
-    T.delta_x = reinterpret_cast<const double*>(base + o_dx);
-    T.sqrt_info = reinterpret_cast<const double*>(base + o_J);
-    T.lin_point = reinterpret_cast<const double*>(base + o_lin);
-    T.lin_extr = reinterpret_cast<const double*>(base + o_lex);
-    T.seen = reinterpret_cast<const uint8_t*>(base + o_seen);
-    T.r = r ? reinterpret_cast<double*>(base + o_r) : nullptr;
-    T.J_ref = J_ref ? reinterpret_cast<double*>(base + o_jr) : nullptr;
-    T.J_other = J_other ? reinterpret_cast<double*>(base + o_jo) : nullptr;
-    T.J_extr = J_extrinsics ? reinterpret_cast<double*>(base + o_je) : nullptr;
-    launch_twopose_extr_eval(T, c->stream);
-    HIPCHK(hipGetLastError());
-    auto down = [&](double* dst, const double* src, size_t bytes) {
-      if (dst && bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    };
-    down(r, T.r, 8 * D * ne);
-    down(J_ref, T.J_ref, 48 * D * ne);
-    down(J_other, T.J_other, 48 * D * ne);
-    down(J_extrinsics, T.J_extr, 48 * D * nc * ne);
-    HIPCHK(hipStreamSynchronize(c->stream));
     return (int)OKVISGPU_OK;
   });
 }
