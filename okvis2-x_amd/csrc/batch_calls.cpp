@@ -7,8 +7,9 @@
 // c->beginBatch (sizes the context's pinned stage and batchScratch, patches the descriptor, stages
 // the inputs), fill what the host computes itself through S.host(), c->uploadBatch (one copy up),
 // launch, c->finishBatch (one copy down, the synchronise, outputs to the caller's arrays).
-// batchScratch is shared by all of them, so an array holds stale bytes of other calls until a
-// kernel writes it: no kernel may read a scratch or output array it has not written.
+// batchScratch is shared by all of them and by the two batch-wide calls of resident_calls.cpp, so
+// an array holds stale bytes of other calls until a kernel writes it: no kernel may read a scratch
+// or output array it has not written.
 #include "runtime.hpp"
 
 #include <algorithm>

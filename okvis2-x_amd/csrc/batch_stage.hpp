@@ -1,6 +1,9 @@
-// batch_stage.hpp — the staging layout of one call-scoped batch (batch_calls.cpp): every array the
-// call's kernels read or write is declared once, with its element type (the device field's) and
-// its element count, against the field of the device struct that will point to it. The layout is
+// batch_stage.hpp — the staging layout of one call's arrays: a call-scoped batch (batch_calls.cpp)
+// or what a batch-wide call on the resident batch takes up and brings down (okvisgpu_update_landmarks
+// and okvisgpu_covisibilities, resident_calls.cpp): the library's one way to place arrays in
+// batchScratch and the pinned stage. Every array the call's kernels read or write is declared once,
+// with its element type (the device field's) and its element count, against the field of the
+// device struct, or the local pointer, that will point to it. The layout is
 // shared by a device buffer and a host staging buffer of the same shape, so that one copy takes
 // every input up and one copy brings every output down:
 //

@@ -1437,6 +1437,53 @@ extern "C" int okvisgpu_plan_assembly(const okvisgpu_problem* problems, int32_t 
   }
 }
 
+// ---- okvisgpu_plan_window (okvisgpu.h): one window's reduced system as analyse() plans it ---------
+extern "C" int okvisgpu_plan_window(const okvisgpu_problem* p, int32_t nested_dissection, int64_t* info,
+                                    uint8_t* tile_nz, int32_t* step_launch, int32_t* natural) {
+  using namespace okg;
+  if (!p) return OKVISGPU_ERR_INVALID_ARGUMENT;
+  try {
+    HostBatch B;
+    B.opt.nd = nested_dissection != 0;
+#ifdef OKG_ANALYSE_TIMING
+    for (double& x : g_atime) x = 0.0;
+    g_alast = std::chrono::steady_clock::now();
+#endif
+    analyse({p}, {}, B);
+#ifdef OKG_ANALYSE_TIMING
+    std::fprintf(stderr, "analyse ms:");
+    for (int i = 0; i < kAnalysePhases; ++i) std::fprintf(stderr, " [%d] %.3f", i, g_atime[i]);
+    std::fprintf(stderr, "\n");
+#endif
+    const int T = B.tileT[0], fpad = B.win_fpad[0];
+    const auto& nz = B.tileNz[0];
+    std::vector<int> L, last;
+    const int nl = cholSchedule(nz, T, L, last);
+    if (info) {
+      int64_t nnz = 0;
+      for (uint8_t v : nz) nnz += v;
+      const int64_t v[8] = {B.win_fnat[0], fpad, T, nnz, nl, B.win_bsplit[0], B.win_bsplit[1], B.win_sgap[1]};
+      std::copy(v, v + 8, info);
+    }
+    if (tile_nz) std::copy(nz.begin(), nz.end(), tile_nz);
+    if (step_launch)
+      for (int k = 0; k < T; ++k) {
+        bool any = false;
+        for (int i = k + 1; i < T && !any; ++i) any = nz[(size_t)i * T + k] != 0;
+        step_launch[k] = any ? L[k] : 0;
+      }
+    if (natural)
+      for (int r = 0; r < fpad; ++r) natural[r] = r < B.win_fdim[0] ? B.f_nat[r] : -1;
+    return OKVISGPU_OK;
+  } catch (const UnsupportedError&) {
+    return OKVISGPU_ERR_UNSUPPORTED;
+  } catch (const ArgError&) {  // (a bad problem: as okvisgpu_plan_digest reports it)
+    return OKVISGPU_ERR_INVALID_ARGUMENT;
+  } catch (const std::exception&) {
+    return OKVISGPU_ERR_INVALID_ARGUMENT;
+  }
+}
+
 // ---- okvisgpu_launch_regime (okvisgpu.h): launchRegime() on plain ints ---------------------------
 extern "C" int okvisgpu_launch_regime(int32_t n_windows, int32_t cu_count, int32_t any_split, int32_t persistent_fits,
                                       int32_t pipe_fits, int32_t cholesky_schedule, int32_t serial_graph,

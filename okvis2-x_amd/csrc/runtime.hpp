@@ -1,14 +1,16 @@
 // runtime.hpp — what the host files behind the C ABI share: the context (okvisgpu_ctx), the error
 // plumbing of the entry points (HIPCHK / HipError, fail, guarded) and the buffers a context owns.
-// runtime.cpp holds the solver path and the entry points that read the resident batch;
-// batch_calls.cpp holds the call-scoped batch entry points, which use a context only for its
+// runtime.cpp holds the solver path; resident_calls.cpp the entry points that read the resident
+// batch; batch_calls.cpp the call-scoped batch entry points, which use a context only for its
 // stream, its pinned staging buffer and batchScratch.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <condition_variable>
 #include <cstdint>
+#include <cstdlib>
 #include <functional>
 #include <map>
 #include <mutex>
@@ -119,6 +121,30 @@ class HostWorkers {
   bool stop_ = false;
 };
 
+// Per-window host copies (parameter staging / write-back) split over host threads: contiguous
+// window ranges, one thread per range. Small batches run on the calling thread. The thread count
+// follows OMP_NUM_THREADS (the job's CPU share) and is capped at 16.
+template <class F>
+void forWindows(int n, F&& fn) {
+  static const int cap = [] {
+    const char* e = std::getenv("OMP_NUM_THREADS");
+    int t = e ? std::atoi(e) : (int)std::thread::hardware_concurrency();
+    return std::max(1, std::min(t, 16));
+  }();
+  const int nt = std::min(cap, n / 64);
+  if (nt <= 1) {
+    for (int w = 0; w < n; ++w) fn(w);
+    return;
+  }
+  std::vector<std::thread> th;
+  th.reserve(nt);
+  for (int t = 0; t < nt; ++t)
+    th.emplace_back([&, t]() {
+      for (int w = (int)((int64_t)n * t / nt); w < (int)((int64_t)n * (t + 1) / nt); ++w) fn(w);
+    });
+  for (auto& x : th) x.join();
+}
+
 }  // namespace okg
 
 struct okvisgpu_ctx {
@@ -167,9 +193,9 @@ struct okvisgpu_ctx {
   int hostBufFactors = 0;
   std::vector<uint8_t> hostFail;
   okg::HostWorkers hostWorkers;
-  // The device arrays of whichever call-scoped entry point is running: the batch calls of
-  // batch_calls.cpp (laid out by a BatchLayout), okvisgpu_update_landmarks and
-  // okvisgpu_covisibilities. The context's own, outside the arena table, grown as needed. Each of
+  // The device arrays of whichever call laid out by a BatchLayout is running: the batch calls of
+  // batch_calls.cpp, okvisgpu_update_landmarks and okvisgpu_covisibilities
+  // (resident_calls.cpp). The context's own, outside the arena table, grown as needed. Each of
   // these calls ends in a stream synchronise, so no two use it at once; what a call finds in it is
   // whatever an earlier call of any of them left, and no kernel reads an array it was not given.
   okg::GrowBuffer batchScratch;
@@ -179,7 +205,7 @@ struct okvisgpu_ctx {
 
   ~okvisgpu_ctx();
 
-  // ---- the staging of one call-scoped batch (batch_stage.hpp): declare, beginBatch, optional fills
+  // ---- the staging of one call's arrays (batch_stage.hpp): declare, beginBatch, optional fills
   // through S.host(), uploadBatch, launch, finishBatch ----
   // Commits the layout, sizes the pinned stage and batchScratch for it, points the declared fields
   // into batchScratch and copies the declared sources into the stage.
@@ -200,7 +226,7 @@ struct okvisgpu_ctx {
   }
   char* paramStage(size_t bytes);
 
-  // ---- the solver path and the calls on the resident batch (runtime.cpp) ----
+  // ---- the solver path (runtime.cpp) ----
   void decideRegime(int schedule);
   void ensureS(hipStream_t s);
   void fillSummaries(const std::vector<okg::WinState>& st, okvisgpu_summary* sums);
@@ -221,7 +247,7 @@ struct okvisgpu_ctx {
   void resetStates(double mu);
   void uploadParams();
   void downloadParams();
-  void updateLandmarks(okvisgpu_landmark_update* U);
+  void updateLandmarks(okvisgpu_landmark_update* U);  // (these two: resident_calls.cpp)
   void covisibilities(okvisgpu_covisibility* V);
   std::vector<okg::WinState> readStates();
   void launchInit(int evalMode);

@@ -1,10 +1,13 @@
-"""The staging of the call-scoped batch entry points (csrc/batch_stage.hpp, csrc/batch_calls.cpp).
+"""The staging of the entry points that bring arrays up and down per call (csrc/batch_stage.hpp: the call-scoped
+batches of csrc/batch_calls.cpp and the calls on the resident batch of csrc/resident_calls.cpp, with the host
+loops of csrc/window_export.hpp).
 
-CPU: BatchLayout alone, in a stand-alone program built with the address and undefined-behaviour sanitizers;
-plain heap blocks stand for the pinned stage and the device buffer and two memcpy for the two copies.
-GPU: the entry points share one device buffer per context, so they are called interleaved on one context
-(small, large, small: a regrow, then a reuse of a larger buffer holding another call's bytes) and every
-result must be the bytes the same call gives alone on a fresh context."""
+CPU: BatchLayout alone, and the export loops alone, each in a stand-alone program built with the address and
+undefined-behaviour sanitizers; plain heap blocks stand for the pinned stage and the device buffer and two memcpy
+for the two copies.
+GPU: the entry points share one pinned stage and one device buffer per context, so they are called interleaved
+on one context (small, large, small: a regrow, then a reuse of a larger buffer holding another call's bytes) and
+every result must be the bytes the same call gives alone on a fresh context."""
 import os
 import shutil
 import subprocess
@@ -207,16 +210,148 @@ def test_batch_layout_under_sanitizers(tmp_path):
     range; every patched field is 256-aligned and inside the range of its kind; empty arrays are distinct and
     non-null; an inout lies in both ranges; null destinations and undeclared optionals are left alone; a write
     to every device output byte arrives at its destination and only there."""
+    _run_under_sanitizers(tmp_path, "layout", LAYOUT_PROGRAM)
+
+
+EXPORT_PROGRAM = r"""
+#include "window_export.hpp"
+
+#include <cmath>
+#include <cstdio>
+#include <vector>
+
+static int failures = 0;
+#define CHECK(x)                                                   \
+  do {                                                             \
+    if (!(x)) {                                                    \
+      std::printf("line %d: %s\n", __LINE__, #x);                  \
+      ++failures;                                                  \
+    }                                                              \
+  } while (0)
+
+// n doubles holding `fill`, with guard doubles on both sides
+struct Guarded {
+  std::vector<double> mem;
+  size_t n;
+  Guarded(size_t count, double fill) : mem(count + 16, -12345.0), n(count) {
+    for (size_t i = 0; i < n; ++i) mem[8 + i] = fill;
+  }
+  double* data() { return mem.data() + 8; }
+  double operator[](size_t i) const { return mem[8 + i]; }
+  bool guardsIntact() const {
+    for (size_t i = 0; i < 8; ++i)
+      if (mem[i] != -12345.0 || mem[8 + n + i] != -12345.0) return false;
+    return true;
+  }
+};
+
+int main() {
+  const int fdim = 7, fpad = 8, dn = 5;
+  const int32_t nat[fpad] = {3, -1, 0, 4, -1, 1, 2, 0};  // rows 1 and 4 are gap rows; [7] is padding, not read
+  const double poison = std::nan(""), untouched = 777.0;
+
+  {  // vector scatter: every natural element written from its row, nothing else
+    double v[fpad];
+    for (int r = 0; r < fdim; ++r) v[r] = 10.0 * r + 1.0;
+    v[7] = poison;
+    Guarded out(dn, untouched);
+    okg::scatterNatural(v, nat, fdim, out.data());
+    for (int r = 0; r < fdim; ++r)
+      if (nat[r] >= 0) CHECK(out[nat[r]] == 10.0 * r + 1.0);
+    CHECK(out.guardsIntact());
+    // the first five rows only: natural elements 1 and 2 (rows 5 and 6) stay as they were
+    Guarded part(dn, untouched);
+    okg::scatterNatural(v, nat, 5, part.data());
+    CHECK(part[3] == 1.0 && part[0] == 21.0 && part[4] == 31.0);
+    CHECK(part[1] == untouched && part[2] == untouched && part.guardsIntact());
+  }
+
+  {  // symmetric scatter: the lower triangle of rows 0..6 is the only part of M that is read
+    std::vector<double> M((size_t)fpad * fpad, poison);
+    for (int r = 0; r < fdim; ++r)
+      for (int q = 0; q <= r; ++q) M[(size_t)r * fpad + q] = 100.0 * r + q + 1.0;
+    Guarded out((size_t)dn * dn, untouched);
+    okg::scatterNaturalSym(M.data(), nat, fdim, fpad, dn, out.data());
+    CHECK(out.guardsIntact());
+    for (int r = 0; r < fdim; ++r)
+      for (int q = 0; q <= r; ++q) {
+        if (nat[r] < 0 || nat[q] < 0) continue;
+        CHECK(out[(size_t)nat[r] * dn + nat[q]] == 100.0 * r + q + 1.0);
+        CHECK(out[(size_t)nat[q] * dn + nat[r]] == 100.0 * r + q + 1.0);
+      }
+    for (int a = 0; a < dn; ++a)
+      for (int b = 0; b < dn; ++b) {
+        const double x = out[(size_t)a * dn + b];
+        CHECK(x == x && x != untouched);            // filled, and from no poisoned element
+        CHECK(x == out[(size_t)b * dn + a]);        // symmetric
+        const int r = (int)(x - 1.0) / 100, q = (int)(x - 1.0) % 100;
+        CHECK(r != 1 && r != 4 && q != 1 && q != 4);  // no gap row or column arrived
+      }
+  }
+
+  {  // record split
+    const size_t n = 3;
+    const int K = 11, R = 4;
+    std::vector<double> rec(n * K);
+    for (size_t f = 0; f < n; ++f)
+      for (int i = 0; i < K; ++i) rec[f * K + i] = 1000.0 * f + i;
+    auto rOk = [&](const Guarded& r) {
+      for (size_t f = 0; f < n; ++f)
+        for (int i = 0; i < R; ++i)
+          if (r[f * R + i] != 1000.0 * f + i) return false;
+      return r.guardsIntact();
+    };
+    auto jOk = [&](const Guarded& J) {
+      for (size_t f = 0; f < n; ++f)
+        for (int i = R; i < K; ++i)
+          if (J[f * (K - R) + (i - R)] != 1000.0 * f + i) return false;
+      return J.guardsIntact();
+    };
+    auto allAre = [](const Guarded& g, double x) {
+      for (size_t i = 0; i < g.n; ++i)
+        if (g[i] != x) return false;
+      return g.guardsIntact();
+    };
+    Guarded r(n * R, untouched), J(n * (K - R), untouched);
+    okg::splitRecords(rec.data(), n, K, R, r.data(), J.data());
+    CHECK(rOk(r) && jOk(J));
+    Guarded r1(n * R, untouched), J1(n * (K - R), untouched);
+    okg::splitRecords(rec.data(), n, K, R, nullptr, J1.data());
+    CHECK(jOk(J1));
+    okg::splitRecords(rec.data(), n, K, R, r1.data(), nullptr);
+    CHECK(rOk(r1));
+    // no records: a null source is not read and the outputs stay as they were
+    Guarded r0(n * R, untouched), J0(n * (K - R), untouched);
+    okg::splitRecords(nullptr, 0, K, R, r0.data(), J0.data());
+    okg::splitRecords(nullptr, 0, K, R, nullptr, nullptr);
+    CHECK(allAre(r0, untouched) && allAre(J0, untouched));
+  }
+  if (failures) return 1;
+  std::printf("ok\n");
+  return 0;
+}
+"""
+
+
+def _run_under_sanitizers(tmp_path, name, program):
     if not shutil.which("g++"):
         pytest.skip("g++ unavailable")
-    src = tmp_path / "layout.cpp"
-    src.write_text(LAYOUT_PROGRAM)
-    exe = tmp_path / "layout"
+    src = tmp_path / (name + ".cpp")
+    src.write_text(program)
+    exe = tmp_path / name
     subprocess.run(["g++", "-std=c++17", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-I", CSRC, str(src), "-o",
                     str(exe)], check=True)
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.strip() == "ok", run.stdout + run.stderr
+
+
+def test_window_export_under_sanitizers(tmp_path):
+    """The host loops of csrc/window_export.hpp alone (no HIP): the natural-order scatter of a vector and of a
+    symmetric matrix over an order with two gap rows and a padded stride (values, untouched elements, guard
+    bytes, symmetry, nothing read from the upper triangle or the padding), and the record split with either
+    output null and with no records."""
+    _run_under_sanitizers(tmp_path, "window_export", EXPORT_PROGRAM)
 
 
 # ------------------------------------------------------------------------------------------ GPU
@@ -269,6 +404,116 @@ def test_gpu_interleaved_calls_share_one_buffer(og, oracle):
             fresh = og.Context(0)
             try:
                 alone = _flat(calls[name](fresh))
+            finally:
+                fresh.close()
+            assert got.keys() == alone.keys() and len(got) > 0, name
+            for k in got:
+                assert got[k] == alone[k], (name, k)
+    finally:
+        shared.close()
+
+
+# ---- the calls on the resident batch (csrc/resident_calls.cpp) use the same two buffers
+COVIS_KEYS = ("counts", "n_observed", "visible", "n_pairs", "n_visible", "any", "path")
+LANDMARK_KEYS = ("quality", "initialised", "reset", "n_initialised", "n_reset", "in_front")
+PARAMS = ("poses", "speed_biases", "landmarks", "imu_state")  # what a call may write of the caller's arrays
+
+
+def _by_window(results, keys):
+    return {f"{w}.{k}": np.ascontiguousarray(r[k]).tobytes() for w, r in enumerate(results) for k in keys}
+
+
+def _params(qs):
+    return {f"{w}.{k}": getattr(q, k).tobytes() for w, q in enumerate(qs) for k in PARAMS}
+
+
+def _resident_windows(og):
+    """Three small windows, so that every base offset of the last one is non-zero: the crafted covisibility
+    window below one 64-landmark word, the smallest window on the tiled count path, the 10-keyframe window."""
+    import test_covisibilities as tcv
+    return [tcv._crafted(og), tcv._window(og, "tiled"), tcv._window(og, "s10")]
+
+
+def _update_landmarks_without_errors(og, ctx, qs):
+    """okvisgpu_update_landmarks with obs_error NULL in every window (the Python wrapper always asks for it)."""
+    import ctypes as C
+    ups = (og.LandmarkUpdate * len(qs))()
+    out = []
+    for u, q in zip(ups, qs):
+        d = {"quality": np.zeros(len(q.landmarks)), "initialised": np.zeros(len(q.landmarks), dtype=np.uint8),
+             "reset": np.zeros(len(q.landmarks), dtype=np.uint8)}
+        u.quality = og.dptr(d["quality"])
+        u.initialised = d["initialised"].ctypes.data_as(C.POINTER(C.c_uint8))
+        u.reset = d["reset"].ctypes.data_as(C.POINTER(C.c_uint8))
+        out.append(d)
+    assert og.lib().okvisgpu_update_landmarks(ctx.h, ups) == 0
+    for u, d in zip(ups, out):
+        d["n_initialised"], d["n_reset"], d["in_front"] = int(u.n_initialised), int(u.n_reset), int(u.in_front)
+    return out
+
+
+def _resident_steps(og, oracle):
+    """(name, (ctx, qs) -> the call's result as bytes), in the order they run on the shared context."""
+    batch = _calls(og, oracle)
+
+    def covis(ctx, qs, masks=None):
+        res = ctx.covisibilities(masks, n_windows=3)
+        assert [r["path"] for r in res] == [0, 1, 0]
+        return _by_window(res, COVIS_KEYS)
+
+    def masks(qs):  # (no mask for the middle window: its part of the staged mask is zero-filled)
+        return [(np.arange(len(qs[0].landmarks)) % 3 == 0).astype(np.uint8), None,
+                (np.arange(len(qs[2].landmarks)) % 5 == 1).astype(np.uint8)]
+
+    def named(prefix, arrays):
+        return {f"{prefix}.{i}": np.ascontiguousarray(a).tobytes() for i, a in enumerate(arrays)}
+
+    return [
+        ("covisibilities", covis),
+        ("place_match", lambda ctx, qs: _flat(batch["place_match"](ctx))),
+        ("update_landmarks(obs_error)",
+         lambda ctx, qs: {**_by_window(ctx.update_landmarks(n_windows=3), LANDMARK_KEYS + ("obs_error",)), **_params(qs)}),
+        ("eval_imu", lambda ctx, qs: {**named("imu", ctx.eval_imu(qs[2].struct.n_imu, window=2)), **_params(qs)}),
+        ("covisibilities(masks)", lambda ctx, qs: covis(ctx, qs, masks(qs))),
+        ("linearize_reduce", lambda ctx, qs: named("lin", ctx.linearize_reduce(window=2))),
+        ("match_frames", lambda ctx, qs: _flat(batch["match_frames"](ctx))),
+        ("update_landmarks",
+         lambda ctx, qs: {**_by_window(_update_landmarks_without_errors(og, ctx, qs), LANDMARK_KEYS), **_params(qs)}),
+        ("eval_relpose+eval_reprojection",
+         lambda ctx, qs: {**named("relpose", ctx.eval_relpose(qs[2].struct.n_relpose, window=2)),
+                          **named("reprojection", ctx.eval_reprojection(qs[2].struct.n_observations, window=2))}),
+        ("gauss_newton_step", lambda ctx, qs: named("gn", ctx.gauss_newton_step(window=2))),
+    ]
+
+
+@pytest.mark.gpu
+def test_gpu_resident_calls_share_the_buffers_of_the_batch_calls(og, oracle):
+    """One context holds three windows; covisibilities, update_landmarks (with and without obs_error), eval_imu,
+    linearize_reduce, eval_relpose, eval_reprojection and gauss_newton_step of the last window run on it
+    interleaved with place_match and match_frames, which use the same pinned stage and device buffer. Each result
+    (with the parameter arrays a call may write) is, byte for byte, what the same call gives on a fresh context
+    holding the same three problems. Every call starts from the same parameter values on both sides: the shared
+    context's arrays are restored and uploaded again, the fresh context gets fresh copies."""
+    if og.device_count() < 1:
+        pytest.fail("no GPU visible: the -m gpu tests must run on the MI355X box")
+    from _problem import OwnedProblem
+    base = _resident_windows(og)
+    assert [q.struct.n_landmarks > 0 and q.struct.n_imu > 0 for q in base] == [True] * 3
+    snaps = [q.snapshot() for q in base]
+    qs = [OwnedProblem.copy_of(q.struct) for q in base]
+    shared = og.Context(0)
+    try:
+        shared.set_problems([q.struct for q in qs])
+        for name, call in _resident_steps(og, oracle):
+            for q, s in zip(qs, snaps):
+                q.restore(s)
+            shared.update_params()
+            got = call(shared, qs)
+            fresh = og.Context(0)
+            try:
+                ps = [OwnedProblem.copy_of(q.struct) for q in base]
+                fresh.set_problems([p.struct for p in ps])
+                alone = call(fresh, ps)
             finally:
                 fresh.close()
             assert got.keys() == alone.keys() and len(got) > 0, name

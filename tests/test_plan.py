@@ -1,4 +1,4 @@
-"""Host-side plan of a window's reduced system (okvisgpu_plan_window; runtime.cpp analyse, chooseNd,
+"""Host-side plan of a window's reduced system (okvisgpu_plan_window; plan.cpp analyse, chooseNd,
 cholSchedule), checked on the CPU against invariants restated here independently:
 
   - the natural order is the identity; the nested-dissection order is a permutation of the same
