@@ -528,6 +528,119 @@ typedef struct okvisgpu_imu_propagate_batch {
 } okvisgpu_imu_propagate_batch;
 int okvisgpu_imu_propagate(okvisgpu_ctx* ctx, const okvisgpu_imu_propagate_batch* batch, int32_t* steps);
 
+/* ---------------------------------------------------------------- LiDAR motion undistortion
+ * (An addition to ABI 6: a new entry point and two new structs; OKVISGPU_ABI_VERSION stays 6.)
+ * LidarMotionUndistortion::deskew (okvis_mapping/src/LidarMotionUndistortion.cpp:27-85; timer "8.1 Live
+ * undistortion" of ThreadedSlam.cpp:785-818) for a batch of independent scans on the GPU, with the
+ * BatchedLidarPropagator behind it (okvis_common/src/ViInterface.cpp:635-798); the per-query pose,
+ * speed and omega_S are also what Trajectory::getStates (ViInterface.cpp:233-348) asks of the same
+ * propagator for the submapping thread (SubmappingInterface.cpp:1255-1268).
+ *
+ * A scan is a state (pose0 = T_WS, speed_bias0) at t_start, the IMU samples around it, and queries: the
+ * stamps of its LiDAR points in non-decreasing order, each with its ray in the LiDAR frame. Per query
+ * the state is propagated from t_start to the query's stamp T and the ray is moved into the live sensor
+ * frame: point = (T_live^-1 T_WS(T) T_SL [ray; 1]) (:79-81), in double (point_f64) and cast to float
+ * (point). The reference's serial loop is restated per query; that is exact because deskew and
+ * getStates never change T_WS_0 / speedAndBias_0 and re-set the propagator's reference biases to the
+ * same values on every appendTo, so Delta_b = 0 and every bias-Jacobian term is multiplied by zero.
+ *   step(k, tau, T), ts[k] < T <= ts[k+1], tau < T (:660-715): with (w0, a0) and (w1, a1) the samples k
+ *   and k+1: if T < ts[k+1], dt = T - tau, r = dt / (ts[k+1] - ts[k]) and (w1, a1) <- (1-r)(w0, a0) +
+ *   r (w1, a1) (dt from tau, as written at :674-681), else dt = ts[k+1] - tau; then r' = dt / (T - ts[k])
+ *   and (w0, a0) <- r' (w0, a0) + (1-r') (w1, a1) (:686-691; exact when tau = ts[k]); then the trapezoid
+ *   chain of :696-715 on Delta_q, acc_integral and acc_doubleintegral with omega_S_true = (w0+w1)/2 -
+ *   b_g. All time differences go through Duration::toSec of the integer nanosecond difference.
+ *   The committed chain starts at the identity with tau = t_start; for k = 0..N-2, if ts[k+1] > tau the
+ *   state after interval k is step(k, tau, ts[k+1]) and tau = ts[k+1], else the interval is skipped
+ *   (:683-685). It depends on the scan's samples, t_start and biases only.
+ *   Query T < t_start: valid = 0, every output of the query zero (deskew skips the point, :61); such
+ *   queries are counted in n_before. T = t_start: valid = 1, pose and speed are the input bits, omega_S
+ *   = 0. T beyond the scan's last sample: valid = 0, zeros (appendTo returns false, :653). Otherwise
+ *   valid = 1: with k the largest index with ts[k] < T, step(k, max(t_start, ts[k]), T) from the
+ *   committed state before interval k, then getState (:762-798): Dt = T - t_start, r = r0 + v0 Dt -
+ *   g_W Dt^2 / 2 + C_WS0 acc_doubleintegral, q = normalised(q0 Delta_q), v = v0 - g_W Dt + C_WS0
+ *   acc_integral, omega_S = omega_S_true, with g_W = (0, 0, g) and C_WS0 from the normalised q0. The
+ *   reference hard-codes g = 9.81 (:768).
+ * Deviation: a query at exactly t_start that is not the scan's first point. The reference
+ * takes the state itself only for the first point (:52-57); for a later point at t_start its sample loop
+ * finds no step with dt > 0, runs off the end of the IMU deque and leaves the propagator unusable for
+ * the rest of the scan. Here every query at t_start is the state itself.
+ *
+ * ray, pose_live and T_SL may be NULL when result->point and ->point_f64 are NULL (the getStates use).
+ * Every output may be NULL. n_scans = 0 and scans without queries are valid. Independent of the problem
+ * set with okvisgpu_set_problems (needs none, leaves the device parameter sets alone); uses the
+ * context's device and stream and returns with the results in the caller's arrays. A scan's result does
+ * not depend on the rest of the batch and is the same bits on every run.
+ * OKVISGPU_ERR_INVALID_ARGUMENT, before anything is launched or written, for a NULL ctx, batch or
+ * result, a missing array, a negative count, a CSR not starting at 0 or not monotone, a scan with
+ * queries but fewer than two samples, a first sample newer than t_start (the assertion at
+ * LidarMotionUndistortion.cpp:34), sample or query stamps of a scan that decrease (the reference's
+ * iterator cannot go back), a non-finite g, and between okvisgpu_solve_begin and _solve_end;
+ * okvisgpu_last_error names the scan and the query or sample. */
+typedef struct okvisgpu_lidar_deskew_batch {
+  int32_t n_scans;
+  double g;                         /* the reference: 9.81                                         */
+  const double* pose0;              /* [n_scans][7] T_WS at t_start                                */
+  const double* speed_bias0;        /* [n_scans][9]                                                */
+  const int64_t* t_start_ns;        /* [n_scans]                                                   */
+  const int32_t* sample_begin;      /* [n_scans+1] CSR into the sample arrays                      */
+  const int64_t* sample_t_ns;       /* [n_samples]                                                 */
+  const double* sample_gyr_acc;     /* [n_samples][6]                                              */
+  const int32_t* query_begin;       /* [n_scans+1] CSR into the query arrays                       */
+  const int64_t* query_t_ns;        /* [n_queries] non-decreasing within a scan                    */
+  const double* ray;                /* [n_queries][3] rayMeasurement, LiDAR frame; see above       */
+  const double* pose_live;          /* [n_scans][7] T_WS of the live frame; see above              */
+  const double* T_SL;               /* [n_scans][7]; see above                                     */
+} okvisgpu_lidar_deskew_batch;
+
+typedef struct okvisgpu_lidar_deskew_result {  /* caller-owned, any may be NULL */
+  uint8_t* valid;                   /* [n_queries]                                                 */
+  float* point;                     /* [n_queries][3] the deskewed ray (:79-81)                    */
+  double* point_f64;                /* [n_queries][3] the same before the cast                     */
+  double* pose;                     /* [n_queries][7] T_WS at the query's stamp                    */
+  double* speed;                    /* [n_queries][3] v_W                                          */
+  double* omega_S;                  /* [n_queries][3]                                              */
+  int32_t* n_before;                /* [n_scans] queries older than t_start                        */
+} okvisgpu_lidar_deskew_result;
+int okvisgpu_lidar_deskew(okvisgpu_ctx* ctx, const okvisgpu_lidar_deskew_batch* batch,
+                          okvisgpu_lidar_deskew_result* result);
+
+/* ---------------------------------------------------------------- voxel-grid downsampling
+ * (An addition to ABI 6: a new entry point and two new structs; OKVISGPU_ABI_VERSION stays 6.)
+ * VoxelDownSample<float> (okvis_mapping/include/okvis/VoxelGridFilter.hpp:46-67; timer "8.3
+ * Downsampling", LidarMotionUndistortion::downsample :87-103) for a batch of clouds on the GPU: keep[i]
+ * = 1 for the first point, in input order, of every voxel of its cloud, among the points with use[i] !=
+ * 0 (use = NULL: all; the host's filterObserved result, so that the deskewed array need not be
+ * compacted). The voxel of a point is, per component, the single-precision quotient p /
+ * float(voxel_size), correctly rounded (Eigen promotes the double divisor to the expression's float
+ * scalar; lattice points sit on voxel faces, so a reciprocal multiply would move them), truncated toward
+ * zero to int32: the voxels around 0 are double width, as in the reference. A point with a non-finite
+ * component or a quotient outside int32 is never kept (undefined behaviour in the reference).
+ * Deviation: the kept points are reported in input order; the reference emits them in
+ * std::unordered_map iteration order, which is implementation-defined, and then subsamples randomly
+ * (downsamplePointCloud, which stays with the caller).
+ * Either output may be NULL. n_clouds = 0 and empty clouds are valid. Independent of the problem set
+ * with okvisgpu_set_problems; uses the context's device and stream and returns with the results in the
+ * caller's arrays. A cloud's result does not depend on the rest of the batch and is the same bits on
+ * every run. OKVISGPU_ERR_INVALID_ARGUMENT, before anything is launched or written, for a NULL ctx,
+ * batch or result, a missing array, a negative count, cloud_begin not starting at 0 or not monotone, a
+ * voxel_size that is not finite and positive (okvisgpu_last_error names the cloud), more than 2^29
+ * points, and between okvisgpu_solve_begin and _solve_end. OKVISGPU_ERR_DEVICE if the hash table ran
+ * out of slots (it holds two per point, so it cannot). */
+typedef struct okvisgpu_voxel_downsample_batch {
+  int32_t n_clouds;
+  const int32_t* cloud_begin;       /* [n_clouds+1] CSR into the point arrays                      */
+  const float* point;               /* [n_points][3]                                               */
+  const double* voxel_size;         /* [n_clouds]                                                  */
+  const uint8_t* use;               /* [n_points] or NULL = all                                    */
+} okvisgpu_voxel_downsample_batch;
+
+typedef struct okvisgpu_voxel_downsample_result {  /* caller-owned, either may be NULL */
+  uint8_t* keep;                    /* [n_points]                                                  */
+  int32_t* n_kept;                  /* [n_clouds]                                                  */
+} okvisgpu_voxel_downsample_result;
+int okvisgpu_voxel_downsample(okvisgpu_ctx* ctx, const okvisgpu_voxel_downsample_batch* batch,
+                              okvisgpu_voxel_downsample_result* result);
+
 /* ---------------------------------------------------------------- map matching
  * (An addition to ABI 6: a new entry point and two new structs; OKVISGPU_ABI_VERSION stays 6.)
  * The matching of Frontend::matchToMap (okvis_frontend/src/Frontend.cpp:1299-1741) on the GPU: the

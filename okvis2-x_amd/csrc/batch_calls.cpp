@@ -1,5 +1,5 @@
 // batch_calls.cpp — the call-scoped batch entry points of the okvisgpu C ABI: each takes a batch of
-// independent items in the caller's arrays, runs one or two kernels over it and returns the results;
+// independent items in the caller's arrays, runs a few kernels over it and returns the results;
 // nothing of the resident problem (okvisgpu_set_problems) is read or written.
 //
 // Every call has the same shape: validate, declare each array once in a BatchLayout
@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <stdexcept>
 
 #include "launch.hpp"
 #include "loss.hpp"
@@ -196,6 +197,144 @@ int okvisgpu_imu_propagate(okvisgpu_ctx* c, const okvisgpu_imu_propagate_batch* 
       if (A->covariance) std::memcpy(A->covariance + 225 * i, S.host(cov) + 225 * i, 1800);
       if (A->jacobian) std::memcpy(A->jacobian + 225 * i, S.host(jac) + 225 * i, 1800);
     }
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_lidar_deskew(okvisgpu_ctx* c, const okvisgpu_lidar_deskew_batch* A, okvisgpu_lidar_deskew_result* R) {
+  if (!c || !A || !R || A->n_scans < 0) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "lidar_deskew: bad arguments");
+  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "lidar_deskew: call after solve_end");
+  if (!std::isfinite(A->g)) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "lidar_deskew: g is not finite");
+  if (A->n_scans == 0) return OKVISGPU_OK;
+  if (!A->pose0 || !A->speed_bias0 || !A->t_start_ns || !A->sample_begin || !A->query_begin)
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "lidar_deskew: missing arrays");
+  return guarded(c, [&]() {
+    const std::string who = "lidar_deskew: ";
+    const size_t n = (size_t)A->n_scans;
+    checkCsr(A->sample_begin, n, "sample_begin", "scan", who);
+    checkCsr(A->query_begin, n, "query_begin", "scan", who);
+    const size_t ns = (size_t)A->sample_begin[n], nq = (size_t)A->query_begin[n];
+    const bool points = R->point || R->point_f64;
+    if (ns && (!A->sample_t_ns || !A->sample_gyr_acc)) throw ArgError{who + "sample arrays missing"};
+    if (nq && !A->query_t_ns) throw ArgError{who + "query_t_ns missing"};
+    if (nq && points && (!A->ray || !A->pose_live || !A->T_SL))
+      throw ArgError{who + "ray, pose_live and T_SL are needed for the point outputs"};
+    std::vector<int32_t> before(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+      const int32_t s0 = A->sample_begin[i], s1 = A->sample_begin[i + 1];
+      const int32_t q0 = A->query_begin[i], q1 = A->query_begin[i + 1];
+      const std::string scan = who + "scan " + std::to_string(i);
+      if (q1 > q0 && s1 - s0 < 2) throw ArgError{scan + " has queries but fewer than two samples"};
+      if (s1 > s0 && A->sample_t_ns[s0] > A->t_start_ns[i])  // (LidarMotionUndistortion.cpp:34)
+        throw ArgError{scan + ": first sample " + std::to_string(A->sample_t_ns[s0]) + " !<= t_start " +
+                       std::to_string(A->t_start_ns[i])};
+      for (int32_t s = s0 + 1; s < s1; ++s)
+        if (A->sample_t_ns[s] < A->sample_t_ns[s - 1])
+          throw ArgError{scan + ": sample stamps decrease at sample " + std::to_string(s - s0)};
+      for (int32_t q = q0; q < q1; ++q) {
+        if (q > q0 && A->query_t_ns[q] < A->query_t_ns[q - 1])
+          throw ArgError{scan + ": query stamps decrease at query " + std::to_string(q - q0)};
+        before[i] += A->query_t_ns[q] < A->t_start_ns[i];
+      }
+    }
+    if (!nq) {  // nothing to propagate
+      if (R->n_before) std::fill(R->n_before, R->n_before + n, 0);
+      return (int)OKVISGPU_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    LidarDeskewDev D{};
+    D.n_scans = A->n_scans;
+    D.n_query = (int32_t)nq;
+    D.g = A->g;
+    BatchLayout S;
+    S.in(D.pose0, A->pose0, 7 * n);
+    S.in(D.sb0, A->speed_bias0, 9 * n);
+    S.in(D.t_start, A->t_start_ns, n);
+    S.in(D.sbegin, A->sample_begin, n + 1);
+    S.in(D.ts, A->sample_t_ns, ns);
+    S.in(D.ga, A->sample_gyr_acc, 6 * ns);
+    S.in(D.qbegin, A->query_begin, n + 1);
+    const auto qScan = S.in(D.q_scan, nullptr, nq);
+    S.in(D.qt, A->query_t_ns, nq);
+    if (points) {
+      S.in(D.ray, A->ray, 3 * nq);
+      S.in(D.pose_live, A->pose_live, 7 * n);
+      S.in(D.T_SL, A->T_SL, 7 * n);
+    }
+    if (R->valid) S.out(D.valid, R->valid, nq);
+    if (R->point) S.out(D.point, R->point, 3 * nq);
+    if (R->point_f64) S.out(D.point_f64, R->point_f64, 3 * nq);
+    if (R->pose) S.out(D.pose, R->pose, 7 * nq);
+    if (R->speed) S.out(D.speed, R->speed, 3 * nq);
+    if (R->omega_S) S.out(D.omega, R->omega_S, 3 * nq);
+    S.scratch(D.table, (size_t)kLidarRow * ns);  // written by the chain kernel, read by the point kernel
+    c->beginBatch(S);
+    for (size_t i = 0; i < n; ++i)  // the scan of every query
+      for (int32_t q = A->query_begin[i]; q < A->query_begin[i + 1]; ++q) S.host(qScan)[q] = (int32_t)i;
+    c->uploadBatch(S);
+    launch_lidar_chain(D, c->stream);
+    HIPCHK(hipGetLastError());
+    launch_lidar_points(D, c->stream);
+    HIPCHK(hipGetLastError());
+    c->finishBatch(S);
+    if (R->n_before) std::copy(before.begin(), before.end(), R->n_before);
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_voxel_downsample(okvisgpu_ctx* c, const okvisgpu_voxel_downsample_batch* A,
+                              okvisgpu_voxel_downsample_result* R) {
+  if (!c || !A || !R || A->n_clouds < 0)
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "voxel_downsample: bad arguments");
+  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "voxel_downsample: call after solve_end");
+  if (A->n_clouds == 0) return OKVISGPU_OK;
+  if (!A->cloud_begin || !A->voxel_size)
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "voxel_downsample: missing arrays");
+  return guarded(c, [&]() {
+    const std::string who = "voxel_downsample: ";
+    const size_t n = (size_t)A->n_clouds;
+    checkCsr(A->cloud_begin, n, "cloud_begin", "cloud", who);
+    const size_t np = (size_t)A->cloud_begin[n];
+    if (np && !A->point) throw ArgError{who + "point missing"};
+    if (np > ((size_t)1 << 29)) throw ArgError{who + "more than 2^29 points"};
+    std::vector<float> vsize(n);
+    for (size_t i = 0; i < n; ++i) {
+      if (!(std::isfinite(A->voxel_size[i]) && A->voxel_size[i] > 0.0))
+        throw ArgError{who + "voxel_size of cloud " + std::to_string(i) + " is not finite and positive"};
+      vsize[i] = (float)A->voxel_size[i];  // Eigen promotes the divisor to the expression's scalar
+    }
+    if (!np) {
+      if (R->n_kept) std::fill(R->n_kept, R->n_kept + n, 0);
+      return (int)OKVISGPU_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    VoxelDev D{};
+    D.n_points = (int32_t)np;
+    D.n_clouds = A->n_clouds;
+    D.table_size = 64;
+    while ((size_t)D.table_size < 2 * np) D.table_size *= 2;
+    BatchLayout S;
+    const auto ptCloud = S.in(D.pt_cloud, nullptr, np);
+    S.in(D.point, A->point, 3 * np);
+    S.in(D.vsize, vsize.data(), n);
+    if (A->use) S.in(D.use, A->use, np);
+    // delivered below, once the error word is known to be clear
+    const auto keep = S.out(D.keep, nullptr, np);
+    const auto kept = S.out(D.n_kept, nullptr, n);
+    const auto err = S.out(D.err, nullptr, 1);
+    S.scratch(D.table, (size_t)D.table_size);
+    S.scratch(D.best, (size_t)D.table_size);
+    S.scratch(D.slot, np);
+    c->beginBatch(S);
+    for (size_t i = 0; i < n; ++i)  // the cloud of every point
+      for (int32_t p = A->cloud_begin[i]; p < A->cloud_begin[i + 1]; ++p) S.host(ptCloud)[p] = (int32_t)i;
+    c->uploadBatch(S);
+    launch_voxel_downsample(D, c->stream);
+    HIPCHK(hipGetLastError());
+    c->finishBatch(S);
+    if (*S.host(err)) throw std::runtime_error("voxel_downsample: hash table exhausted");
+    if (R->keep) std::memcpy(R->keep, S.host(keep), np);
+    if (R->n_kept) std::memcpy(R->n_kept, S.host(kept), sizeof(int32_t) * n);
     return (int)OKVISGPU_OK;
   });
 }

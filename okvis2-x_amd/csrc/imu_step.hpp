@@ -1,0 +1,50 @@
+// imu_step.hpp — what the IMU stepping kernels share (kernels_imu_propagate.hip, kernels_lidar.hip):
+// one sample as stored with its clamped prefetch load, the inputs of one trapezoid step and the
+// step's dq (ImuError.cpp:644-650; ViInterface.cpp:696-703 is the same text).
+#pragma once
+
+#include "okvisgpu_math.hpp"
+
+namespace okg {
+
+struct RawSample {  // one sample as stored: stamp, gyro, accelerometer
+  int64_t t;
+  double ga[6];
+};
+// Sample min(k, N - 1) of the N > 0 samples that start at sbeg. The loops keep samples k and k + 1 in
+// registers and load sample k + 2 at the top of step k, so that a step does not begin by waiting for
+// its own loads. (Past the end the last sample stands in: the reference reads nothing it uses there,
+// such a step has dt <= 0.)
+__device__ __forceinline__ RawSample loadRawSample(const int64_t* ts, const double* ga, int sbeg, int N, int k) {
+  const int s = sbeg + min(k, N - 1);
+  RawSample r;
+  r.t = gmem(ts)[s];
+  const auto g = gmem(ga + 6 * (size_t)s);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) r.ga[j] = g[j];
+  return r;
+}
+
+// One step's inputs: dt, the bias-corrected mean rates, the step's end and the saturation flags.
+struct PropStep {
+  double dt, w[3], a[3];  // dt, omega_S_true, acc_S_true (:645, :655)
+  bool gyr_sat, acc_sat;
+  int64_t nexttime;
+};
+
+// dq of one step (:644-650) and sin / cos of theta_half for the right Jacobian
+__device__ __forceinline__ Q stepDq(const PropStep& s, double& sh, double& ch) {
+  const double theta_half = sqrt(s.w[0] * s.w[0] + s.w[1] * s.w[1] + s.w[2] * s.w[2]) * 0.5 * s.dt;
+  sincos(theta_half, &sh, &ch);
+  double sincv;  // ode::sinc (ode.hpp:34-46)
+  if (fabs(theta_half) > 1.0e-6) {
+    sincv = sh / theta_half;
+  } else {
+    const double x_2 = theta_half * theta_half, x_4 = x_2 * x_2, x_6 = x_2 * x_2 * x_2;
+    sincv = 1.0 - (1.0 / 6.0) * x_2 + (1.0 / 120.0) * x_4 - (1.0 / 5040.0) * x_6;
+  }
+  const double sth = sincv * 0.5 * s.dt;
+  return Q{sth * s.w[0], sth * s.w[1], sth * s.w[2], ch};
+}
+
+}  // namespace okg

@@ -18,6 +18,7 @@
 // (:552-553); an item with no integrated step keeps its pose and speed/bias bits (Jacobian = I,
 // covariance = 0).
 #include "imu_fdelta.hpp"
+#include "imu_step.hpp"
 #include "launch.hpp"
 #include "okvisgpu_math.hpp"
 
@@ -42,30 +43,13 @@ __device__ __forceinline__ PropItem loadItem(const ImuPropagateDev& A, int i) {
   return it;
 }
 
+// Sample min(k, N - 1) of the item (the prefetch of imu_step.hpp, which also has PropStep and stepDq).
+__device__ __forceinline__ RawSample loadSample(const ImuPropagateDev& A, const PropItem& it, int k) {
+  return loadRawSample(A.ts, A.ga, it.sbeg, it.N, k);
+}
 // One pass of the sample loop up to the integrity check (:584-640) for sample k of an item whose
 // integration time is `time`: false when the sample is skipped (dt <= 0, :607-609). On true: dt, the
 // (interpolated) measurements, the step's end `nexttime` and the saturation flags.
-struct PropStep {
-  double dt, w[3], a[3];  // dt, omega_S_true, acc_S_true (:645, :655)
-  bool gyr_sat, acc_sat;
-  int64_t nexttime;
-};
-struct RawSample {  // one sample as stored: stamp, gyro, accelerometer
-  int64_t t;
-  double ga[6];
-};
-// Sample min(k, N - 1) of the item. The loops keep samples k and k + 1 in registers and load sample
-// k + 2 at the top of step k, so that a step does not begin by waiting for its own loads. (Past the
-// end the last sample stands in: the reference reads nothing it uses there, such a step has dt <= 0.)
-__device__ __forceinline__ RawSample loadSample(const ImuPropagateDev& A, const PropItem& it, int k) {
-  const int s = it.sbeg + min(k, it.N - 1);
-  RawSample r;
-  r.t = gmem(A.ts)[s];
-  const auto g = gmem(A.ga + 6 * (size_t)s);
-#pragma unroll
-  for (int j = 0; j < 6; ++j) r.ga[j] = g[j];
-  return r;
-}
 __device__ __forceinline__ bool propSample(const ImuPropagateDev& A, const PropItem& it, int k, const RawSample& cur,
                                            const RawSample& nxt, int64_t time, bool started, const double* bg,
                                            const double* ba, PropStep& s) {
@@ -114,21 +98,6 @@ __device__ __forceinline__ bool propSample(const ImuPropagateDev& A, const PropI
   s.dt = dt;
   s.nexttime = nexttime;
   return true;
-}
-
-// dq of one step (:644-650) and sin / cos of theta_half for the right Jacobian
-__device__ __forceinline__ Q stepDq(const PropStep& s, double& sh, double& ch) {
-  const double theta_half = sqrt(s.w[0] * s.w[0] + s.w[1] * s.w[1] + s.w[2] * s.w[2]) * 0.5 * s.dt;
-  sincos(theta_half, &sh, &ch);
-  double sincv;  // ode::sinc (ode.hpp:34-46)
-  if (fabs(theta_half) > 1.0e-6) {
-    sincv = sh / theta_half;
-  } else {
-    const double x_2 = theta_half * theta_half, x_4 = x_2 * x_2, x_6 = x_2 * x_2 * x_2;
-    sincv = 1.0 - (1.0 / 6.0) * x_2 + (1.0 / 120.0) * x_4 - (1.0 / 5040.0) * x_6;
-  }
-  const double sth = sincv * 0.5 * s.dt;
-  return Q{sth * s.w[0], sth * s.w[1], sth * s.w[2], ch};
 }
 
 // The outputs that need no Jacobian (:726-732), written by one lane: r_1, q_1 = normalize(q_0 Dq)

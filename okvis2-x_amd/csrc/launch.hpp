@@ -40,6 +40,58 @@ struct ImuPropagateDev {
   int32_t* steps;
 };
 void launch_imu_propagate(const ImuPropagateDev& A, hipStream_t s);
+// LidarMotionUndistortion::deskew / Trajectory::getStates for a batch of scans (kernels_lidar.hip;
+// okvisgpu_lidar_deskew). Device arrays in the layout of okvisgpu_lidar_deskew_batch, plus q_scan
+// [n_query] = the scan of every query. launch_lidar_chain: one lane per scan that has queries writes
+// table [n_samples][kLidarRow] (Delta_q, acc_integral, acc_doubleintegral before every sample's
+// interval; rows of a scan without queries are not written and not read). launch_lidar_points: one
+// lane per query; every element of every output that is not nullptr is written. ray / pose_live /
+// T_SL are read only when point or point_f64 is set.
+constexpr int kLidarRow = 10;
+struct LidarDeskewDev {
+  int32_t n_scans, n_query;
+  double g;
+  const double* pose0;
+  const double* sb0;
+  const int64_t* t_start;
+  const int32_t* sbegin;
+  const int64_t* ts;
+  const double* ga;
+  const int32_t* qbegin;
+  const int32_t* q_scan;
+  const int64_t* qt;
+  const double* ray;
+  const double* pose_live;
+  const double* T_SL;
+  double* table;
+  uint8_t* valid;
+  float* point;
+  double* point_f64;
+  double* pose;
+  double* speed;
+  double* omega;
+};
+void launch_lidar_chain(const LidarDeskewDev& L, hipStream_t s);
+void launch_lidar_points(const LidarDeskewDev& L, hipStream_t s);
+// VoxelDownSample for a batch of clouds (kernels_lidar.hip; okvisgpu_voxel_downsample): the first
+// point, in input order, of every (cloud, voxel). pt_cloud [n_points] = the cloud of every point,
+// vsize [n_clouds] = float(voxel_size), use [n_points] or nullptr (all). table / best [table_size]
+// (a power of two >= 2 n_points) and slot [n_points] are scratch; the three kernels write every
+// element of table, best, slot, keep, n_kept and err [1] (non-zero: the probe ran out of slots).
+struct VoxelDev {
+  int32_t n_points, n_clouds, table_size;
+  const int32_t* pt_cloud;
+  const float* point;
+  const float* vsize;
+  const uint8_t* use;
+  int32_t* table;
+  int32_t* best;
+  int32_t* slot;
+  uint8_t* keep;
+  int32_t* n_kept;
+  int32_t* err;
+};
+void launch_voxel_downsample(const VoxelDev& V, hipStream_t s);
 // host-evaluated factors: gather the evaluation points (host_in), scatter the uploaded results
 // (host_out) into the linearisation records; the host step between them is the runtime's
 void launch_host_gather(const DevProblem& P, int mode, hipStream_t s);

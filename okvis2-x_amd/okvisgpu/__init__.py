@@ -28,6 +28,7 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _lp = C.POINTER(C.c_int64)
 _up = C.POINTER(C.c_uint8)
+_fp = C.POINTER(C.c_float)
 
 
 class Camera(C.Structure):
@@ -195,6 +196,29 @@ class ImuPropagateBatch(C.Structure):
                 ("sample_gyr_acc", _dp), ("covariance", _dp), ("jacobian", _dp)]
 
 
+class LidarDeskewBatch(C.Structure):
+    """okvisgpu_lidar_deskew_batch: scans (a state, IMU samples, stamped rays) to undistort."""
+    _fields_ = [("n_scans", C.c_int32), ("g", C.c_double), ("pose0", _dp), ("speed_bias0", _dp), ("t_start_ns", _lp),
+                ("sample_begin", _ip), ("sample_t_ns", _lp), ("sample_gyr_acc", _dp), ("query_begin", _ip),
+                ("query_t_ns", _lp), ("ray", _dp), ("pose_live", _dp), ("T_SL", _dp)]
+
+
+class LidarDeskewResult(C.Structure):
+    """okvisgpu_lidar_deskew_result: the caller-owned outputs of okvisgpu_lidar_deskew (any may be NULL)."""
+    _fields_ = [("valid", _up), ("point", _fp), ("point_f64", _dp), ("pose", _dp), ("speed", _dp), ("omega_S", _dp),
+                ("n_before", _ip)]
+
+
+class VoxelDownsampleBatch(C.Structure):
+    """okvisgpu_voxel_downsample_batch: point clouds, each with its voxel size."""
+    _fields_ = [("n_clouds", C.c_int32), ("cloud_begin", _ip), ("point", _fp), ("voxel_size", _dp), ("use", _up)]
+
+
+class VoxelDownsampleResult(C.Structure):
+    """okvisgpu_voxel_downsample_result: the caller-owned outputs of okvisgpu_voxel_downsample."""
+    _fields_ = [("keep", _up), ("n_kept", _ip)]
+
+
 class MatchBatch(C.Structure):
     """okvisgpu_match_batch: one map and the jobs (camera image x pass) matched against it."""
     _fields_ = [("n_poses", C.c_int32), ("poses", _dp), ("n_cameras", C.c_int32), ("cameras", C.POINTER(Camera)),
@@ -296,7 +320,7 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_launch_regime", "okvisgpu_update_landmarks", "okvisgpu_covisibilities", "okvisgpu_imu_propagate",
     "okvisgpu_twopose_extrinsics_compute", "okvisgpu_twopose_extrinsics_evaluate", "okvisgpu_gauss_newton_step",
     "okvisgpu_match_to_map", "okvisgpu_plan_assembly", "okvisgpu_match_frames", "okvisgpu_place_match",
-    "okvisgpu_place_refine",
+    "okvisgpu_place_refine", "okvisgpu_lidar_deskew", "okvisgpu_voxel_downsample",
 ]
 N_PHASES = 15
 TWOPOSE_MAX_CAMERAS = 6
@@ -364,6 +388,9 @@ def lib():
         L.okvisgpu_plan_assembly.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, _ip, C.c_int32, _ip, _lp]
         L.okvisgpu_imu_append.argtypes = [C.c_void_p, C.POINTER(ImuAppendBatch), _ip]
         L.okvisgpu_imu_propagate.argtypes = [C.c_void_p, C.POINTER(ImuPropagateBatch), _ip]
+        L.okvisgpu_lidar_deskew.argtypes = [C.c_void_p, C.POINTER(LidarDeskewBatch), C.POINTER(LidarDeskewResult)]
+        L.okvisgpu_voxel_downsample.argtypes = [C.c_void_p, C.POINTER(VoxelDownsampleBatch),
+                                                C.POINTER(VoxelDownsampleResult)]
         L.okvisgpu_match_to_map.argtypes = [C.c_void_p, C.POINTER(MatchBatch), C.POINTER(MatchResult)]
         L.okvisgpu_match_frames.argtypes = [C.c_void_p, C.POINTER(FrameMatchBatch), C.POINTER(FrameMatchResult)]
         L.okvisgpu_place_match.argtypes = [C.c_void_p, C.POINTER(PlaceMatchBatch), C.POINTER(PlaceMatchResult)]
@@ -623,6 +650,41 @@ def imu_propagate_batch(imu_params, poses, speed_biases, t_start, t_end, sample_
     return b, keep + [poses, speed_biases, covariance, jacobian]
 
 
+def lidar_deskew_batch(pose0, speed_bias0, t_start, sample_begin, sample_t, sample_ga, query_begin, query_t, ray=None,
+                       pose_live=None, T_SL=None, g=9.81):
+    """An okvisgpu_lidar_deskew_batch over numpy arrays (copied to the struct's types where they differ):
+    (struct, arrays it points into). `ray` [n_queries, 3], `pose_live` and `T_SL` [n_scans, 7] may be None
+    (NULL) when no point output is asked for; `g` is the reference's hard-coded 9.81 by default."""
+    f8 = lambda a, *shape: np.ascontiguousarray(a, dtype=np.float64).reshape(*shape)
+    i4 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    i8 = lambda a: np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+    k = {"pose0": f8(pose0, -1, 7), "speed_bias0": f8(speed_bias0, -1, 9), "t_start_ns": i8(t_start),
+         "sample_begin": i4(sample_begin), "sample_t_ns": i8(sample_t), "sample_gyr_acc": f8(sample_ga, -1, 6),
+         "query_begin": i4(query_begin), "query_t_ns": i8(query_t)}
+    for name, a, cols in (("ray", ray, 3), ("pose_live", pose_live, 7), ("T_SL", T_SL, 7)):
+        if a is not None:
+            k[name] = f8(a, -1, cols)
+    b = LidarDeskewBatch()
+    b.n_scans, b.g = len(k["t_start_ns"]), float(g)
+    _set_arrays(b, k)
+    return b, k
+
+
+def voxel_downsample_batch(cloud_begin, point, voxel_size, use=None):
+    """An okvisgpu_voxel_downsample_batch over numpy arrays (copied to the struct's types where they
+    differ): (struct, arrays it points into). `point` [n_points, 3] float32, `voxel_size` [n_clouds],
+    `use` [n_points] or None = NULL (every point)."""
+    k = {"cloud_begin": np.ascontiguousarray(cloud_begin, dtype=np.int32).reshape(-1),
+         "point": np.ascontiguousarray(point, dtype=np.float32).reshape(-1, 3),
+         "voxel_size": np.ascontiguousarray(voxel_size, dtype=np.float64).reshape(-1)}
+    if use is not None:
+        k["use"] = np.ascontiguousarray(use, dtype=np.uint8).reshape(-1)
+    b = VoxelDownsampleBatch()
+    b.n_clouds = len(k["cloud_begin"]) - 1
+    _set_arrays(b, k)
+    return b, k
+
+
 def match_batch(poses, cameras, extrinsics, landmarks, landmark_quality, obs_begin, obs_pose, obs_camera,
                 obs_descriptor, obs_ray, job_camera, job_pass, job_pose_prepare, job_pose_match, kp_begin, keypoint,
                 descriptor, ray, ray_valid, landmark, landmark_use=None, imu_use=True, loop_closure=False,
@@ -684,7 +746,8 @@ def frame_match_batch(cameras, job_mode, job_camera0, job_camera1, job_pose0, jo
 
 def _set_arrays(b, arrays):
     for name, a in arrays.items():
-        ptr = {np.dtype(np.float64): _dp, np.dtype(np.int32): _ip, np.dtype(np.uint8): _up}[a.dtype]
+        ptr = {np.dtype(np.float64): _dp, np.dtype(np.int32): _ip, np.dtype(np.uint8): _up, np.dtype(np.int64): _lp,
+               np.dtype(np.float32): _fp}[a.dtype]
         setattr(b, name, a.ctypes.data_as(ptr))
 
 
@@ -997,6 +1060,39 @@ class Context:
                     "okvisgpu_imu_propagate")
         out = (steps,) + ((P,) if P is not None else ()) + ((J,) if J is not None else ())
         return out[0] if len(out) == 1 else out
+
+    def lidar_deskew(self, batch: LidarDeskewBatch, fill=None, outputs=None):
+        """okvisgpu_lidar_deskew (LidarMotionUndistortion::deskew and the per-ray states of
+        Trajectory::getStates) for a batch built by lidar_deskew_batch(): dict of valid [n_queries] (uint8),
+        point [n_queries, 3] (float32), point_f64 [n_queries, 3], pose [n_queries, 7], speed, omega_S
+        [n_queries, 3], n_before [n_scans]. `outputs` names the outputs to ask for (the others are passed as
+        NULL and left out of the dict; default: all, without the points when the batch has no rays); `fill`
+        (a dict of per-output values) pre-fills the arrays the call writes into."""
+        n = batch.n_scans
+        nq = int(batch.query_begin[n]) if batch.query_begin and n > 0 else 0
+        spec = {"valid": ((nq,), np.uint8), "point": ((nq, 3), np.float32), "point_f64": ((nq, 3), np.float64),
+                "pose": ((nq, 7), np.float64), "speed": ((nq, 3), np.float64), "omega_S": ((nq, 3), np.float64),
+                "n_before": ((n,), np.int32)}
+        if outputs is None:
+            outputs = [k for k in spec if batch.ray or k not in ("point", "point_f64")]
+        out = {k: np.full(spec[k][0], (fill or {}).get(k, 0), dtype=spec[k][1]) for k in spec if k in outputs}
+        r = LidarDeskewResult()
+        _set_arrays(r, out)
+        self._check(lib().okvisgpu_lidar_deskew(self.h, C.byref(batch), C.byref(r)), "okvisgpu_lidar_deskew")
+        return out
+
+    def voxel_downsample(self, batch: VoxelDownsampleBatch, fill=None):
+        """okvisgpu_voxel_downsample (VoxelDownSample<float>) for a batch built by voxel_downsample_batch():
+        dict of keep [n_points] (uint8: the first point, in input order, of its voxel) and n_kept [n_clouds].
+        `fill` (a dict of per-output values) pre-fills the arrays the call writes into."""
+        n = batch.n_clouds
+        npts = int(batch.cloud_begin[n]) if batch.cloud_begin and n > 0 else 0
+        out = {"keep": np.full(npts, (fill or {}).get("keep", 0), dtype=np.uint8),
+               "n_kept": np.full(n, (fill or {}).get("n_kept", 0), dtype=np.int32)}
+        r = VoxelDownsampleResult()
+        _set_arrays(r, out)
+        self._check(lib().okvisgpu_voxel_downsample(self.h, C.byref(batch), C.byref(r)), "okvisgpu_voxel_downsample")
+        return out
 
     def match_to_map(self, batch: MatchBatch, fill=None):
         """okvisgpu_match_to_map (Frontend::matchToMap's candidate preparation and both matching passes)
