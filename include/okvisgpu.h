@@ -528,6 +528,95 @@ typedef struct okvisgpu_imu_propagate_batch {
 } okvisgpu_imu_propagate_batch;
 int okvisgpu_imu_propagate(okvisgpu_ctx* ctx, const okvisgpu_imu_propagate_batch* batch, int32_t* steps);
 
+/* ---------------------------------------------------------------- GNSS factors
+ * (An addition to ABI 6: a new entry point and two new structs; OKVISGPU_ABI_VERSION stays 6.)
+ * The factor ViGraph::addGpsMeasurement (ViGraph.cpp:973-1006) adds for every GPS fix, evaluated for a
+ * batch of independent factors on the GPU at given parameter values: kind 0 is
+ * GpsErrorAsynchronous::EvaluateWithMinimalJacobians (GpsErrorAsynchronous.cpp:98-300) with its own IMU
+ * pre-integration from the state's stamp t_k to the fix's stamp t_g (redoPreintegration, :303-507), kind 1
+ * GpsErrorSynchronous (GpsErrorSynchronous.cpp:41-144). Parameters per factor: poses[i] = T_WS at t_k
+ * ([r, q xyzw]), speed_biases[i], and T_GW[gw_index[i]] (gw_index NULL: block 0 for every factor, so that
+ * one call serves the realtime and the full graph); the antenna offset r_SA (gpsParameters_.r_SA) is the
+ * call's. `information` is the constructor's argument, the fix's inverse covariance.
+ *
+ * Kind 0, per factor, on its `state` (layout below; state NULL: every factor is fresh and nothing is kept):
+ *   Redo decision (:134-142): Delta_b = speed_bias[3:9] - ref[3:9]; redo = flag || |Delta_b_g| > 0.0003;
+ *   the factor re-integrates if redo_propagation_always || (redo && n_samples < 50) || counter == 0. After
+ *   a redo the counter is incremented, Delta_b = 0, the flag is 0 and ref is the current speed/biases;
+ *   without one the flag keeps `redo` and nothing else of the state changes.
+ *   Redo chain (:303-507): the stepping rules of :341-375 and :480-483 (interpolation at both ends, steps
+ *   with dt <= 0 skipped, dt from integer nanosecond differences through Duration::toSec), the saturation
+ *   factors of :378-398 (100 for a step with a gyro resp. accelerometer component above g_max resp.
+ *   a_max), the trapezoid chain and the bias Jacobians of :402-432 (dalpha_db_g with the right Jacobian),
+ *   and with use_imu_covariance the recursion X <- F_delta X F_delta^T + K (:437-467), the symmetrisation
+ *   and the sigma-weighted sum P_delta (:494-500); without it P_delta stays zero (:331).
+ *   Then (:145-166) T_WS(t_g) = (r + v Dt - g_W Dt^2 / 2 + C_WS (acc_doubleintegral + dp_db_g Delta_b_g -
+ *   C_doubleintegral Delta_b_a), normalised(q Delta_q deltaQ(-dalpha_db_g Delta_b_g))) with Dt = t_g - t_k,
+ *   g_W = (0, 0, g) and C_WS from the normalised q, and Jprop as at :156-166. With use_imu_covariance
+ *   (:173-187) P = T P_delta T^T, Jws = [C_GW, -C_GW [C_WS r_SA]x], covOverall = information^-1 + Jws P_66
+ *   Jws^T and sqrt_info = LLT(covOverall^-1).L^T; without (:192-193) sqrt_info = LLT((information^-1)^-1).L^T.
+ *   error = z - (C_GW (r_tg + C_tg r_SA) + r_GW), r = sqrt_info error, and the Jacobians exactly as
+ *   :213-294: sqrt_info is not differentiated. C_GW is toRotationMatrix of T_GW's quaternion as stored.
+ * Kind 1 (GpsErrorSynchronous.cpp:41-144): sqrt_info = LLT(information).L^T, error = z - (C_GW (r + C_WS r_SA)
+ * + r_GW) with both rotation matrices from the quaternions as stored; speed_biases, the stamps, the samples,
+ * state and the two flags are ignored, J_speed_bias is zero and steps 0.
+ *
+ * Deviations: (1) the four dPdsigma_ matrices are carried as their sigma-weighted sum (the
+ * recursion and the symmetrisation are linear, and the reference reads dPdsigma_ nowhere else). (2) A factor
+ * whose samples do not reach t_g (the reference then evaluates uninitialised members: :137-141 ignores the
+ * -1), whose first sample is newer than t_k (the assertion at :311), or with t_g < t_k is an argument error;
+ * these are the assertions of ViGraph.cpp:976-982. (3) With t_g == t_k the reference's loop reads (it + 1)
+ * past the end and uses nothing of it; here the result is 0 steps, identity increments and P_delta = 0.
+ *
+ * State, OKVISGPU_GPS_STATE_DOUBLES per factor: [0..65] as OKVISGPU_IMU_STATE_DOUBLES (redo counter, redo
+ * flag, Delta_q, C_integral, C_doubleintegral, acc_integral, acc_doubleintegral, dalpha_db_g, dv_db_g,
+ * dp_db_g, speedAndBiases_ref_), [66] the steps of the last redo, [67..291] P_delta_ (15x15 row-major).
+ * cross_ is not kept: nothing reads it after a redo, because this functor has no append.
+ *
+ * OKVISGPU_ERR_INVALID_ARGUMENT, before anything is launched or written, for a NULL ctx, batch or result, a
+ * missing array, a negative count, n_gw < 1, a gw_index outside [0, n_gw), an unknown kind, an `information`
+ * that is not finite, symmetric (to 1e-12 of its largest entry) and positive definite (a 3x3 Cholesky on
+ * the host), for kind 0 a sample_begin not starting at 0 or not monotone and the cases of deviation 2, and
+ * between okvisgpu_solve_begin and _solve_end; okvisgpu_last_error names the factor. n = 0 is valid.
+ * Independent of the problem set with okvisgpu_set_problems (needs none, leaves the device parameter sets
+ * alone); uses the context's device and stream and returns with the results in the caller's arrays. A
+ * factor's result does not depend on the rest of the batch and is the same bits on every run. */
+#define OKVISGPU_GPS_STATE_DOUBLES 292
+typedef struct okvisgpu_gps_batch {
+  int32_t n;
+  int32_t kind;                     /* 0 GpsErrorAsynchronous, 1 GpsErrorSynchronous               */
+  int32_t use_imu_covariance;       /* the reference's static useImuCovariance (default true)      */
+  int32_t redo_propagation_always;  /* the reference's static redoPropagationAlways                */
+  okvisgpu_imu_params imu_params;
+  double r_SA[3];                   /* gpsParameters_.r_SA                                         */
+  const double* poses;              /* [n][7] T_WS at t_k                                          */
+  const double* speed_biases;       /* [n][9]                                                      */
+  int32_t n_gw;
+  const double* T_GW;               /* [n_gw][7]                                                   */
+  const int32_t* gw_index;          /* [n] or NULL = block 0                                       */
+  const double* measurement;        /* [n][3]                                                      */
+  const double* information;        /* [n][9] row-major                                            */
+  const int64_t* t_k_ns;            /* [n]                                                         */
+  const int64_t* t_g_ns;            /* [n]                                                         */
+  const int32_t* sample_begin;      /* [n+1] CSR into the sample arrays                            */
+  const int64_t* sample_t_ns;       /* [n_samples]                                                 */
+  const double* sample_gyr_acc;     /* [n_samples][6]                                              */
+  double* state;                    /* [n][OKVISGPU_GPS_STATE_DOUBLES] in/out, NULL = fresh        */
+} okvisgpu_gps_batch;
+
+typedef struct okvisgpu_gps_result {  /* caller-owned, any may be NULL; Jacobians row-major */
+  double* r;                        /* [n][3]                                                      */
+  double* error;                    /* [n][3] the unweighted error, error()                        */
+  double* sqrt_info;                /* [n][9]                                                      */
+  double* J_pose;                   /* [n][3][6] jacobiansMinimal[0]                               */
+  double* J_speed_bias;             /* [n][3][9] jacobiansMinimal[1]                               */
+  double* J_T_GW;                   /* [n][3][6] jacobiansMinimal[2]                               */
+  double* J_pose_ambient;           /* [n][3][7] minimal x PoseManifold::minusJacobian: jacobians[0] */
+  double* J_T_GW_ambient;           /* [n][3][7] jacobians[2]                                      */
+  int32_t* steps;                   /* [n] integrated steps of this call's redo, else the stored value */
+} okvisgpu_gps_result;
+int okvisgpu_gps_evaluate(okvisgpu_ctx* ctx, const okvisgpu_gps_batch* batch, okvisgpu_gps_result* result);
+
 /* ---------------------------------------------------------------- LiDAR motion undistortion
  * (An addition to ABI 6: a new entry point and two new structs; OKVISGPU_ABI_VERSION stays 6.)
  * LidarMotionUndistortion::deskew (okvis_mapping/src/LidarMotionUndistortion.cpp:27-85; timer "8.1 Live

@@ -14,11 +14,13 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 
 #include "launch.hpp"
 #include "loss.hpp"
+#include "mat3_spd.hpp"
 
 using namespace okg;
 
@@ -197,6 +199,99 @@ int okvisgpu_imu_propagate(okvisgpu_ctx* c, const okvisgpu_imu_propagate_batch* 
       if (A->covariance) std::memcpy(A->covariance + 225 * i, S.host(cov) + 225 * i, 1800);
       if (A->jacobian) std::memcpy(A->jacobian + 225 * i, S.host(jac) + 225 * i, 1800);
     }
+    return (int)OKVISGPU_OK;
+  });
+}
+
+int okvisgpu_gps_evaluate(okvisgpu_ctx* c, const okvisgpu_gps_batch* A, okvisgpu_gps_result* R) {
+  static_assert(kGpsState == OKVISGPU_GPS_STATE_DOUBLES, "device layout and header layout differ");
+  if (!c || !A || !R || A->n < 0) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "gps_evaluate: bad arguments");
+  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "gps_evaluate: call after solve_end");
+  if (A->kind != 0 && A->kind != 1)
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "gps_evaluate: unknown kind " + std::to_string(A->kind));
+  if (A->n == 0) return OKVISGPU_OK;
+  const bool async = A->kind == 0;
+  if (!A->poses || !A->T_GW || A->n_gw < 1 || !A->measurement || !A->information ||
+      (async && (!A->speed_biases || !A->t_k_ns || !A->t_g_ns || !A->sample_begin)))
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "gps_evaluate: missing arrays");
+  return guarded(c, [&]() {
+    const std::string who = "gps_evaluate: ";
+    const size_t n = (size_t)A->n;
+    size_t ns = 0;
+    if (async) {
+      checkCsr(A->sample_begin, n, "sample_begin", "factor", who);
+      ns = (size_t)A->sample_begin[n];
+      if (ns && (!A->sample_t_ns || !A->sample_gyr_acc)) throw ArgError{who + "sample arrays missing"};
+    }
+    for (size_t i = 0; i < n; ++i) {
+      const std::string fac = who + "factor " + std::to_string(i);
+      if (A->gw_index && (A->gw_index[i] < 0 || A->gw_index[i] >= A->n_gw))
+        throw ArgError{fac + ": gw_index " + std::to_string(A->gw_index[i]) + " outside [0, n_gw)"};
+      const double* G = A->information + 9 * i;
+      double top = 0.0, U[9];
+      bool finite = true;
+      for (int e = 0; e < 9; ++e) {
+        finite = finite && std::isfinite(G[e]);
+        top = std::max(top, std::fabs(G[e]));
+      }
+      if (!finite) throw ArgError{fac + ": information is not finite"};
+      if (std::fabs(G[1] - G[3]) > 1e-12 * top || std::fabs(G[2] - G[6]) > 1e-12 * top || std::fabs(G[5] - G[7]) > 1e-12 * top)
+        throw ArgError{fac + ": information is not symmetric"};
+      if (!chol3U(G, U)) throw ArgError{fac + ": information is not positive definite"};
+      if (!async) continue;
+      // the assertions of ViGraph.cpp:976-982 and GpsErrorAsynchronous.cpp:311-313
+      const int32_t s0 = A->sample_begin[i], s1 = A->sample_begin[i + 1];
+      if (A->t_g_ns[i] < A->t_k_ns[i])
+        throw ArgError{fac + ": t_g " + std::to_string(A->t_g_ns[i]) + " < t_k " + std::to_string(A->t_k_ns[i])};
+      if (s1 == s0) throw ArgError{fac + " has no samples"};
+      if (A->sample_t_ns[s0] > A->t_k_ns[i])
+        throw ArgError{fac + ": first sample " + std::to_string(A->sample_t_ns[s0]) + " !<= t_k " +
+                       std::to_string(A->t_k_ns[i])};
+      if (A->sample_t_ns[s1 - 1] < A->t_g_ns[i])
+        throw ArgError{fac + ": last sample " + std::to_string(A->sample_t_ns[s1 - 1]) + " !>= t_g " +
+                       std::to_string(A->t_g_ns[i])};
+    }
+    HIPCHK(hipSetDevice(c->device));
+    GpsDev D{};
+    D.n = A->n;
+    D.kind = A->kind;
+    D.use_cov = A->use_imu_covariance ? 1 : 0;
+    D.redo_always = A->redo_propagation_always ? 1 : 0;
+    {  // (development: the four-matrix recursion, for the comparison of scripts/gps_timing.py)
+      const char* e = std::getenv("OKVISGPU_GPS_FOUR_P");
+      D.four_p = e && e[0] == '1';
+    }
+    imuParams(A->imu_params, D.par);
+    std::memcpy(D.r_SA, A->r_SA, sizeof(D.r_SA));
+    BatchLayout S;
+    S.in(D.poses, A->poses, 7 * n);
+    S.in(D.T_GW, A->T_GW, 7 * (size_t)A->n_gw);
+    if (A->gw_index) S.in(D.gw_index, A->gw_index, n);
+    S.in(D.meas, A->measurement, 3 * n);
+    S.in(D.info, A->information, 9 * n);
+    if (async) {
+      S.in(D.sb, A->speed_biases, 9 * n);
+      S.in(D.t_k, A->t_k_ns, n);
+      S.in(D.t_g, A->t_g_ns, n);
+      S.in(D.sbegin, A->sample_begin, n + 1);
+      S.in(D.ts, A->sample_t_ns, ns);
+      S.in(D.ga, A->sample_gyr_acc, 6 * ns);
+      if (A->state) S.inout(D.state, A->state, A->state, (size_t)kGpsState * n);
+    }
+    if (R->r) S.out(D.r, R->r, 3 * n);
+    if (R->error) S.out(D.error, R->error, 3 * n);
+    if (R->sqrt_info) S.out(D.sqrt_info, R->sqrt_info, 9 * n);
+    if (R->J_pose) S.out(D.J_pose, R->J_pose, 18 * n);
+    if (R->J_speed_bias) S.out(D.J_sb, R->J_speed_bias, 27 * n);
+    if (R->J_T_GW) S.out(D.J_gw, R->J_T_GW, 18 * n);
+    if (R->J_pose_ambient) S.out(D.J_pose_amb, R->J_pose_ambient, 21 * n);
+    if (R->J_T_GW_ambient) S.out(D.J_gw_amb, R->J_T_GW_ambient, 21 * n);
+    if (R->steps) S.out(D.steps, R->steps, n);
+    c->beginBatch(S);
+    c->uploadBatch(S);
+    launch_gps_evaluate(D, c->stream);
+    HIPCHK(hipGetLastError());
+    c->finishBatch(S);
     return (int)OKVISGPU_OK;
   });
 }

@@ -32,6 +32,59 @@ struct PropStep {
   int64_t nexttime;
 };
 
+// One pass of the sample loop up to the integrity check (ImuError.cpp:584-640; the same text at
+// GpsErrorAsynchronous.cpp:341-398) for sample k of N whose integration time is `time` and ends at
+// t_end: false when the sample is skipped (dt <= 0, :607-609). On true: dt, the (interpolated)
+// measurements less the biases, the step's end `nexttime` and the saturation flags against a_max, g_max.
+__device__ __forceinline__ bool stepSample(double a_max, double g_max, int N, int64_t t_end, int k, const RawSample& cur,
+                                           const RawSample& nxt, int64_t time, bool started, const double* bg,
+                                           const double* ba, PropStep& s) {
+  const bool last = k + 1 == N;
+  double om0[3], ac0[3], om1[3], ac1[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    om0[j] = cur.ga[j];
+    ac0[j] = cur.ga[3 + j];
+    om1[j] = nxt.ga[j];
+    ac1[j] = nxt.ga[3 + j];
+  }
+  const int64_t ts0 = cur.t;
+  int64_t nexttime = last ? t_end : nxt.t;
+  double dt = durToSec(nexttime - time);
+  if (t_end < nexttime) {  // clip to t_end, interpolate the second measurement (:598-605)
+    const double interval = durToSec(nexttime - ts0);
+    nexttime = t_end;
+    dt = durToSec(nexttime - time);
+    const double r = dt / interval;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      om1[j] = (1.0 - r) * om0[j] + r * om1[j];
+      ac1[j] = (1.0 - r) * ac0[j] + r * ac1[j];
+    }
+  }
+  if (!(dt > 0.0)) return false;
+  if (!started) {  // the first integrated step starts at t_start (:612-617)
+    const double r = dt / durToSec(nexttime - ts0);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      om0[j] = r * om0[j] + (1.0 - r) * om1[j];
+      ac0[j] = r * ac0[j] + (1.0 - r) * ac1[j];
+    }
+  }
+  s.gyr_sat = false;
+  s.acc_sat = false;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    s.gyr_sat = s.gyr_sat || fabs(om0[j]) > g_max || fabs(om1[j]) > g_max;
+    s.acc_sat = s.acc_sat || fabs(ac0[j]) > a_max || fabs(ac1[j]) > a_max;
+    s.w[j] = 0.5 * (om0[j] + om1[j]) - bg[j];
+    s.a[j] = 0.5 * (ac0[j] + ac1[j]) - ba[j];
+  }
+  s.dt = dt;
+  s.nexttime = nexttime;
+  return true;
+}
+
 // dq of one step (:644-650) and sin / cos of theta_half for the right Jacobian
 __device__ __forceinline__ Q stepDq(const PropStep& s, double& sh, double& ch) {
   const double theta_half = sqrt(s.w[0] * s.w[0] + s.w[1] * s.w[1] + s.w[2] * s.w[2]) * 0.5 * s.dt;

@@ -48,56 +48,11 @@ __device__ __forceinline__ RawSample loadSample(const ImuPropagateDev& A, const 
   return loadRawSample(A.ts, A.ga, it.sbeg, it.N, k);
 }
 // One pass of the sample loop up to the integrity check (:584-640) for sample k of an item whose
-// integration time is `time`: false when the sample is skipped (dt <= 0, :607-609). On true: dt, the
-// (interpolated) measurements, the step's end `nexttime` and the saturation flags.
+// integration time is `time` (stepSample, imu_step.hpp): false when the sample is skipped.
 __device__ __forceinline__ bool propSample(const ImuPropagateDev& A, const PropItem& it, int k, const RawSample& cur,
                                            const RawSample& nxt, int64_t time, bool started, const double* bg,
                                            const double* ba, PropStep& s) {
-  const bool last = k + 1 == it.N;
-  double om0[3], ac0[3], om1[3], ac1[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    om0[j] = cur.ga[j];
-    ac0[j] = cur.ga[3 + j];
-    om1[j] = nxt.ga[j];
-    ac1[j] = nxt.ga[3 + j];
-  }
-  const int64_t ts0 = cur.t;
-  int64_t nexttime = last ? it.t_end : nxt.t;
-  double dt = durToSec(nexttime - time);
-  if (it.t_end < nexttime) {  // clip to t_end, interpolate the second measurement (:598-605)
-    const double interval = durToSec(nexttime - ts0);
-    nexttime = it.t_end;
-    dt = durToSec(nexttime - time);
-    const double r = dt / interval;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      om1[j] = (1.0 - r) * om0[j] + r * om1[j];
-      ac1[j] = (1.0 - r) * ac0[j] + r * ac1[j];
-    }
-  }
-  if (!(dt > 0.0)) return false;
-  if (!started) {  // the first integrated step starts at t_start (:612-617)
-    const double r = dt / durToSec(nexttime - ts0);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      om0[j] = r * om0[j] + (1.0 - r) * om1[j];
-      ac0[j] = r * ac0[j] + (1.0 - r) * ac1[j];
-    }
-  }
-  const double g_max = A.par[1], a_max = A.par[0];
-  s.gyr_sat = false;
-  s.acc_sat = false;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    s.gyr_sat = s.gyr_sat || fabs(om0[j]) > g_max || fabs(om1[j]) > g_max;
-    s.acc_sat = s.acc_sat || fabs(ac0[j]) > a_max || fabs(ac1[j]) > a_max;
-    s.w[j] = 0.5 * (om0[j] + om1[j]) - bg[j];
-    s.a[j] = 0.5 * (ac0[j] + ac1[j]) - ba[j];
-  }
-  s.dt = dt;
-  s.nexttime = nexttime;
-  return true;
+  return stepSample(A.par[0], A.par[1], it.N, it.t_end, k, cur, nxt, time, started, bg, ba, s);
 }
 
 // The outputs that need no Jacobian (:726-732), written by one lane: r_1, q_1 = normalize(q_0 Dq)

@@ -40,6 +40,41 @@ struct ImuPropagateDev {
   int32_t* steps;
 };
 void launch_imu_propagate(const ImuPropagateDev& A, hipStream_t s);
+// GpsErrorAsynchronous / GpsErrorSynchronous for a batch of factors (kernels_gps.hip;
+// okvisgpu_gps_evaluate). Device arrays in the layout of okvisgpu_gps_batch / _result. kind 1 reads
+// none of sb, t_k, t_g, the samples and state. gw_index and state may be nullptr (block 0; every
+// factor fresh), and so may every output; an output that is set is written for every factor. Of
+// state, a factor that re-integrates gets all kGpsState entries written, one that does not only its
+// redo flag [1]. four_p: the covariance recursion on the reference's four dPdsigma matrices instead
+// of their sigma-weighted sum (scripts/gps_timing.py's comparison; the entry point never sets it).
+constexpr int kGpsState = 292;
+struct GpsDev {
+  int32_t n, kind, use_cov, redo_always, four_p;
+  double par[7];  // a_max, g_max, sigma_g_c, sigma_a_c, sigma_gw_c, sigma_aw_c, g
+  double r_SA[3];
+  const double* poses;
+  const double* sb;
+  const double* T_GW;
+  const int32_t* gw_index;
+  const double* meas;
+  const double* info;
+  const int64_t* t_k;
+  const int64_t* t_g;
+  const int32_t* sbegin;
+  const int64_t* ts;
+  const double* ga;
+  double* state;
+  double* r;
+  double* error;
+  double* sqrt_info;
+  double* J_pose;
+  double* J_sb;
+  double* J_gw;
+  double* J_pose_amb;
+  double* J_gw_amb;
+  int32_t* steps;
+};
+void launch_gps_evaluate(const GpsDev& A, hipStream_t s);
 // LidarMotionUndistortion::deskew / Trajectory::getStates for a batch of scans (kernels_lidar.hip;
 // okvisgpu_lidar_deskew). Device arrays in the layout of okvisgpu_lidar_deskew_batch, plus q_scan
 // [n_query] = the scan of every query. launch_lidar_chain: one lane per scan that has queries writes

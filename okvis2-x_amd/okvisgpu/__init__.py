@@ -19,6 +19,7 @@ REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.environ.get("OKVISGPU_LIB") or os.path.join(PKG_ROOT, "libokvisgpu.so")  # env: A/B builds
 
 IMU_STATE_DOUBLES = 526
+GPS_STATE_DOUBLES = 292
 
 DIST_NONE, DIST_RADTAN, DIST_EQUIDISTANT, DIST_RADTAN8 = 0, 1, 2, 3
 DENSE_SCHUR, SPARSE_NORMAL_CHOLESKY = 0, 1
@@ -196,6 +197,21 @@ class ImuPropagateBatch(C.Structure):
                 ("sample_gyr_acc", _dp), ("covariance", _dp), ("jacobian", _dp)]
 
 
+class GpsBatch(C.Structure):
+    """okvisgpu_gps_batch: GpsErrorAsynchronous (kind 0) / GpsErrorSynchronous (kind 1) factors to evaluate."""
+    _fields_ = [("n", C.c_int32), ("kind", C.c_int32), ("use_imu_covariance", C.c_int32),
+                ("redo_propagation_always", C.c_int32), ("imu_params", ImuParams), ("r_SA", C.c_double * 3),
+                ("poses", _dp), ("speed_biases", _dp), ("n_gw", C.c_int32), ("T_GW", _dp), ("gw_index", _ip),
+                ("measurement", _dp), ("information", _dp), ("t_k_ns", _lp), ("t_g_ns", _lp), ("sample_begin", _ip),
+                ("sample_t_ns", _lp), ("sample_gyr_acc", _dp), ("state", _dp)]
+
+
+class GpsResult(C.Structure):
+    """okvisgpu_gps_result: the caller-owned outputs of okvisgpu_gps_evaluate (any may be NULL)."""
+    _fields_ = [("r", _dp), ("error", _dp), ("sqrt_info", _dp), ("J_pose", _dp), ("J_speed_bias", _dp), ("J_T_GW", _dp),
+                ("J_pose_ambient", _dp), ("J_T_GW_ambient", _dp), ("steps", _ip)]
+
+
 class LidarDeskewBatch(C.Structure):
     """okvisgpu_lidar_deskew_batch: scans (a state, IMU samples, stamped rays) to undistort."""
     _fields_ = [("n_scans", C.c_int32), ("g", C.c_double), ("pose0", _dp), ("speed_bias0", _dp), ("t_start_ns", _lp),
@@ -320,7 +336,7 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_launch_regime", "okvisgpu_update_landmarks", "okvisgpu_covisibilities", "okvisgpu_imu_propagate",
     "okvisgpu_twopose_extrinsics_compute", "okvisgpu_twopose_extrinsics_evaluate", "okvisgpu_gauss_newton_step",
     "okvisgpu_match_to_map", "okvisgpu_plan_assembly", "okvisgpu_match_frames", "okvisgpu_place_match",
-    "okvisgpu_place_refine", "okvisgpu_lidar_deskew", "okvisgpu_voxel_downsample",
+    "okvisgpu_place_refine", "okvisgpu_lidar_deskew", "okvisgpu_voxel_downsample", "okvisgpu_gps_evaluate",
 ]
 N_PHASES = 15
 TWOPOSE_MAX_CAMERAS = 6
@@ -388,6 +404,7 @@ def lib():
         L.okvisgpu_plan_assembly.argtypes = [C.POINTER(Problem), C.c_int32, C.c_int32, _ip, C.c_int32, _ip, _lp]
         L.okvisgpu_imu_append.argtypes = [C.c_void_p, C.POINTER(ImuAppendBatch), _ip]
         L.okvisgpu_imu_propagate.argtypes = [C.c_void_p, C.POINTER(ImuPropagateBatch), _ip]
+        L.okvisgpu_gps_evaluate.argtypes = [C.c_void_p, C.POINTER(GpsBatch), C.POINTER(GpsResult)]
         L.okvisgpu_lidar_deskew.argtypes = [C.c_void_p, C.POINTER(LidarDeskewBatch), C.POINTER(LidarDeskewResult)]
         L.okvisgpu_voxel_downsample.argtypes = [C.c_void_p, C.POINTER(VoxelDownsampleBatch),
                                                 C.POINTER(VoxelDownsampleResult)]
@@ -648,6 +665,42 @@ def imu_propagate_batch(imu_params, poses, speed_biases, t_start, t_end, sample_
     if jacobian is not None:
         b.jacobian = dptr(jacobian)
     return b, keep + [poses, speed_biases, covariance, jacobian]
+
+
+def gps_batch(imu_params, r_SA, poses, T_GW, measurement, information, speed_biases=None, t_k=None, t_g=None,
+              sample_begin=None, sample_t=None, sample_ga=None, gw_index=None, state=None, kind=0,
+              use_imu_covariance=True, redo_propagation_always=False):
+    """An okvisgpu_gps_batch over numpy arrays (copied to the struct's types where they differ): (struct,
+    arrays it points into). `state` [n, GPS_STATE_DOUBLES] float64 C-contiguous is referenced, not copied
+    (updated in place); None = NULL (every factor fresh). `gw_index` None = NULL (block 0). kind 1 needs
+    none of speed_biases, the stamps and the samples."""
+    f8 = lambda a, *shape: np.ascontiguousarray(a, dtype=np.float64).reshape(*shape)
+    k = {"poses": f8(poses, -1, 7), "T_GW": f8(T_GW, -1, 7), "measurement": f8(measurement, -1, 3),
+         "information": f8(information, -1, 9)}
+    n = len(k["poses"])
+    for name, a, conv in (("speed_biases", speed_biases, lambda a: f8(a, -1, 9)),
+                          ("t_k_ns", t_k, lambda a: np.ascontiguousarray(a, dtype=np.int64).reshape(-1)),
+                          ("t_g_ns", t_g, lambda a: np.ascontiguousarray(a, dtype=np.int64).reshape(-1)),
+                          ("sample_begin", sample_begin, lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)),
+                          ("sample_t_ns", sample_t, lambda a: np.ascontiguousarray(a, dtype=np.int64).reshape(-1)),
+                          ("sample_gyr_acc", sample_ga, lambda a: f8(a, -1, 6)),
+                          ("gw_index", gw_index, lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1))):
+        if a is not None:
+            k[name] = conv(a)
+    if state is not None:
+        assert state.dtype == np.float64 and state.flags["C_CONTIGUOUS"] and state.shape == (n, GPS_STATE_DOUBLES)
+        k["state"] = state
+    b = GpsBatch()
+    b.n, b.kind, b.n_gw = n, int(kind), len(k["T_GW"])
+    b.use_imu_covariance, b.redo_propagation_always = int(bool(use_imu_covariance)), int(bool(redo_propagation_always))
+    b.imu_params = imu_params
+    b.r_SA = (C.c_double * 3)(*[float(x) for x in r_SA])
+    _set_arrays(b, k)
+    return b, k
+
+
+GPS_OUTPUTS = {"r": (3,), "error": (3,), "sqrt_info": (3, 3), "J_pose": (3, 6), "J_speed_bias": (3, 9), "J_T_GW": (3, 6),
+               "J_pose_ambient": (3, 7), "J_T_GW_ambient": (3, 7), "steps": ()}
 
 
 def lidar_deskew_batch(pose0, speed_bias0, t_start, sample_begin, sample_t, sample_ga, query_begin, query_t, ray=None,
@@ -1060,6 +1113,22 @@ class Context:
                     "okvisgpu_imu_propagate")
         out = (steps,) + ((P,) if P is not None else ()) + ((J,) if J is not None else ())
         return out[0] if len(out) == 1 else out
+
+    def gps_evaluate(self, batch: GpsBatch, fill=None, outputs=None):
+        """okvisgpu_gps_evaluate (GpsErrorAsynchronous / GpsErrorSynchronous for a batch of factors) for a
+        batch built by gps_batch(): dict of r, error [n, 3], sqrt_info [n, 3, 3], J_pose, J_T_GW [n, 3, 6],
+        J_speed_bias [n, 3, 9], J_pose_ambient, J_T_GW_ambient [n, 3, 7] and steps [n] (int32); the batch's
+        `state` is updated in place. `outputs` names the outputs to ask for (the others are passed as NULL
+        and left out of the dict; default: all); `fill` (a float, e.g. NaN) pre-fills the float arrays the
+        call writes into, and steps with -7."""
+        n = batch.n
+        names = list(GPS_OUTPUTS) if outputs is None else list(outputs)
+        out = {k: (np.full(n, 0 if fill is None else -7, dtype=np.int32) if k == "steps" else
+                   np.full((n,) + GPS_OUTPUTS[k], 0.0 if fill is None else float(fill))) for k in names}
+        r = GpsResult()
+        _set_arrays(r, out)
+        self._check(lib().okvisgpu_gps_evaluate(self.h, C.byref(batch), C.byref(r)), "okvisgpu_gps_evaluate")
+        return out
 
     def lidar_deskew(self, batch: LidarDeskewBatch, fill=None, outputs=None):
         """okvisgpu_lidar_deskew (LidarMotionUndistortion::deskew and the per-ray states of
