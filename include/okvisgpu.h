@@ -131,7 +131,8 @@ int okvisgpu_loss_evaluate(const okvisgpu_loss* loss, double s, double* rho);
  *  [27..29]  acc_doubleintegral       [30..38]  dalpha_db_g
  *  [39..47]  dv_db_g                  [48..56]  dp_db_g
  *  [57..65]  speedAndBiases_ref_ (9)  [66..290] squareRootInformation_ (15x15 row-major)
- *  [291]     steps integrated by the last redo (informational)
+ *  [291]     steps integrated by the last redo (informational; -1: the samples did not reach t1,
+ *            nothing was integrated and the factor evaluates to r = 0, J = 0, ImuError.cpp:849-853)
  *  [292..300] cross_ (row-major)       [301..525] P_delta_ (15x15, symmetric): what
  *            ImuError::append continues from (ABI 4)                                          */
 #define OKVISGPU_IMU_STATE_DOUBLES 526
@@ -188,7 +189,12 @@ typedef struct okvisgpu_problem {
   const int64_t* imu_t0_ns;         /* [n_imu]                                                  */
   const int64_t* imu_t1_ns;         /* [n_imu]                                                  */
   const int32_t* imu_sample_begin;  /* [n_imu+1] CSR into the sample arrays                     */
-  const int64_t* imu_sample_t_ns;   /* [n_samples]                                              */
+  const int64_t* imu_sample_t_ns;   /* [n_samples] a factor's stamps may come in any order: a step is
+                                       integrated from the reference's running `time` (the end of the
+                                       last integrated step) and skipped when it does not advance it
+                                       (ImuError.cpp:315-328, :439), so a duplicate or a stamp that
+                                       steps back gives what ImuError gives. Samples that end before
+                                       t1 leave the factor unintegrated (ImuError.cpp:270-273).    */
   const double* imu_sample_gyr_acc; /* [n_samples][6] gyroscopes(3) accelerometers(3)           */
   okvisgpu_imu_params imu_params;
   double* imu_state;                /* [n_imu][OKVISGPU_IMU_STATE_DOUBLES] in/out, NULL = fresh  */

@@ -192,9 +192,11 @@ static_assert(ImuLds<kImuKFew>::total * 8 * 4 <= 80 * 1024, "two few-window work
 // k_imu_propagate)
 
 // Cyclic Jacobi with round-robin ordering on the 16x16 (15 + decoupled pad) symmetric matrix A of
-// every group with `need` set; V receives the eigenvectors. Uniform control flow over the wave.
+// every group with `need` set; V receives the eigenvectors. Uniform control flow over the wave; a
+// group without `need` writes nothing (its V holds the Cholesky path's U when the wave is mixed).
 __device__ void groupJacobi(double* A, double* V, double* rot, int l, bool need) {
-  for (int e = l; e < 256; e += kImuGroup) V[(e >> 4) * kS + (e & 15)] = ((e >> 4) == (e & 15)) ? 1.0 : 0.0;
+  if (need)
+    for (int e = l; e < 256; e += kImuGroup) V[(e >> 4) * kS + (e & 15)] = ((e >> 4) == (e & 15)) ? 1.0 : 0.0;
   __syncthreads();
   bool run = need;
   for (int sweep = 0; sweep < 100; ++sweep) {
@@ -394,9 +396,10 @@ __device__ __forceinline__ void evalImuBlock(const DevProblem& P, int mode, int 
   // working set in registers (the single-pass form carried ~140 live doubles per lane and spilled):
   //  R  (lane k, parallel)  step record: dt, interpolated samples, dq = exp(w dt), Jr(w dt),
   //                         R(dq)^T, the noise of the step. The integration time before step `it`
-  //                         is t0 for the first sample and max(t0, min(ts[it], t1)) after it: where
-  //                         the previous step ended, or unchanged when that step was skipped for
-  //                         dt <= 0 (ImuError.cpp:339); steps after the one reaching t1 get dt = 0.
+  //                         is the reference's running `time`: t0, then the largest min(ts[j], t1)
+  //                         of the steps so far: where the last integrated step ended, unchanged
+  //                         by a step skipped for dt <= 0 (ImuError.cpp:326), whatever order the
+  //                         stamps have; steps after the one reaching t1 get dt = 0.
   //  Q  (sequential)        Delta_q <- Delta_q dq and cross_ <- R(dq)^T cross_ + Jr dt, the only
   //                         products on the chain (ImuError.cpp:352-392), stored per step;
   //  I  (lane k, parallel)  C, C_1, C + C_1, (C + C_1) a, C_1 Jr, X (ImuError.cpp:360-392) and the
@@ -410,6 +413,8 @@ __device__ __forceinline__ void evalImuBlock(const DevProblem& P, int mode, int 
     Nmax = max(Nmax, __shfl_xor(Nmax, 16, 64));
     Nmax = max(Nmax, __shfl_xor(Nmax, 32, 64));
     bool started = false;  // hasStarted: an earlier step was integrated
+    int64_t tnow = t0;     // `time` (ImuError.cpp:264, :439) after the chunks so far
+    constexpr bool kScanAlways = K <= 4;
     double* const rec = sG + LY::rec;
     double* const q1 = sG + LY::q1;
     double* const cr = sG + LY::cr;
@@ -431,9 +436,13 @@ __device__ __forceinline__ void evalImuBlock(const DevProblem& P, int mode, int 
         bool ok = false;
         double dt = 0.0, om0[3] = {0, 0, 0}, ac0[3] = {0, 0, 0}, om1[3] = {0, 0, 0}, ac1[3] = {0, 0, 0};
         int64_t nexttime = 0;
-        int s0 = sbeg;
-        if (l < K && it < N) {
-          s0 = sbeg + it;
+        const bool mine = l < K && it < N;
+        const int s0 = mine ? sbeg + it : sbeg;
+        int64_t ts0 = t0;
+        bool back = false;  // this step's stamp is older than the one before it
+        if (mine) {
+          ts0 = gmem(P.imu_ts)[s0];
+          if (!kScanAlways && it > 0) back = gmem(P.imu_ts)[s0 - 1] > ts0;
           const int s1 = (it + 1 < N) ? s0 + 1 : s0;
           for (int k = 0; k < 3; ++k) {
             om0[k] = gmem(P.imu_ga)[6 * (size_t)s0 + k];
@@ -442,10 +451,32 @@ __device__ __forceinline__ void evalImuBlock(const DevProblem& P, int mode, int 
             ac1[k] = gmem(P.imu_ga)[6 * (size_t)s1 + 3 + k];
           }
           nexttime = (it + 1 == N) ? t1 : gmem(P.imu_ts)[s0 + 1];
-          const int64_t tb = (it == 0) ? t0 : max(t0, min(gmem(P.imu_ts)[s0], t1));
+        }
+        const int eLast = min(c0 + K, N) - 1;  // the group's last step up to this chunk
+        const int64_t tsEnd = (!kScanAlways && eLast > 0) ? gmem(P.imu_ts)[sbeg + eLast] : t0;
+        // The reference's running `time` before step `it`: max(t0, max over 1 <= j <= it of
+        // min(ts[j], t1)); tnow carries it between chunks (uniform over the group): an inclusive
+        // prefix maximum over the chunk's lanes. While the stamps ascend that is the step's own
+        // stamp, and the chunks of 16 (one or two windows, latency bound) then skip the scan's four
+        // dependent shuffle rounds on a wave-uniform test of two more stamp loads per lane; for the
+        // chunks of four the two rounds cost less than those loads (profiles/imu_error_fix_ab.txt).
+        int64_t tb = (mine && it > 0) ? min(ts0, t1) : t0;
+        if (kScanAlways || __any(back)) {
+#pragma unroll
+          for (int d = 1; d < K; d <<= 1) {
+            const int64_t o = __shfl_up(tb, d, kImuGroup);
+            if (l >= d) tb = max(tb, o);
+          }
+          tb = max(tb, tnow);
+          tnow = __shfl(tb, K - 1, kImuGroup);
+        } else {
+          tb = max(tb, tnow);
+          tnow = max(tnow, min(tsEnd, t1));
+        }
+        if (mine) {
           dt = durToSec(nexttime - tb);
           if (t1 < nexttime) {
-            const double interval = durToSec(nexttime - gmem(P.imu_ts)[s0]);
+            const double interval = durToSec(nexttime - ts0);
             nexttime = t1;
             dt = durToSec(nexttime - tb);
             const double r = dt / interval;
@@ -458,7 +489,7 @@ __device__ __forceinline__ void evalImuBlock(const DevProblem& P, int mode, int 
         }
         const unsigned gm = (unsigned)((__ballot(ok) >> (16 * g)) & 0xFFFFull);
         if (ok && !started && l == __ffs(gm) - 1) {  // the first integrated step starts at t0
-          const double r = dt / durToSec(nexttime - gmem(P.imu_ts)[s0]);
+          const double r = dt / durToSec(nexttime - ts0);
           for (int k = 0; k < 3; ++k) {
             om0[k] = r * om0[k] + (1.0 - r) * om1[k];
             ac0[k] = r * ac0[k] + (1.0 - r) * ac1[k];
@@ -808,6 +839,7 @@ __device__ __forceinline__ void evalImuBlock(const DevProblem& P, int mode, int 
   if (live && l == 0) {
     state[0] = (double)redoCounter;
     state[1] = redo ? 1.0 : 0.0;
+    if (doRedo && !covered) state[291] = -1.0;  // what redoPreintegration returned (ImuError.cpp:272)
   }
 
   // ---- residual and minimal Jacobians (ImuError.cpp:861-1000)
