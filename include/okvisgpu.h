@@ -736,6 +736,100 @@ typedef struct okvisgpu_voxel_downsample_result {  /* caller-owned, either may b
 int okvisgpu_voxel_downsample(okvisgpu_ctx* ctx, const okvisgpu_voxel_downsample_batch* batch,
                               okvisgpu_voxel_downsample_result* result);
 
+/* ---------------------------------------------------------------- keypoint-coverage overlap
+ * (An addition to ABI 6: a new entry point and two new structs; OKVISGPU_ABI_VERSION stays 6.)
+ * The mask painting by which the reference picks a frame's keyframe, decides on a new keyframe and rates
+ * the tracking, for a batch of jobs on the GPU: ViSlamBackend::overlapFraction
+ * (okvis_ceres/src/ViSlamBackend.cpp:2903-2989; the loops of mostOverlappedStateId :2780-2809,
+ * currentLoopclosureStateId :2811-2836, prunePlaceRecognitionFrames :2838-2870 and
+ * Frontend::matchMotionStereo, okvis_frontend/src/Frontend.cpp:1985-2014), the two parts of
+ * Frontend::doWeNeedANewKeyframe (Frontend.cpp:1186-1295) and ViSlamBackend::trackingQuality
+ * (ViSlamBackend.cpp:261-300). Every result is an integer count or one IEEE division of two counts.
+ *
+ * Frames: image_begin is a CSR of camera images per frame; an image has its full-resolution rows and cols
+ * (rows == 0 or cols == 0: image(im).empty()) and, through kp_begin, its keypoints: keypoint =
+ * cv::KeyPoint::pt as getCvKeypoint returns it, landmark = MultiFrame::landmarkId raw (0 = none; whether
+ * the landmark still exists is not looked at, as in overlapFraction), flag read by kind 3 only.
+ * Grid and disc, per image and job: G_r = rows / 10, G_c = cols / 10 (integer division), R =
+ * int(double(min(G_r, G_c)) * factor) truncated. A keypoint's centre is, per component, cvRound(float(
+ * double(pt) * 0.1)), ties to even (Point2f * double is computed in double and stored as float; the
+ * cv::Point conversion is cvRound). The disc is what OpenCV's 8-connected integer Circle() fills for
+ * cv::FILLED (cv::circle with LINE_8 and shift 0), cut to the grid: with the midpoint recurrence (err = 0,
+ * dx = R, dy = 0, plus = 1, minus = 2R - 1; while dx >= dy: visit (dx, dy); dy++, err += plus, plus += 2,
+ * if err > 0 { err -= minus, dx--, minus -= 2 }) and hw[dy] = max(hw[dy], dx), hw[dx] = max(hw[dx], dy)
+ * over the visits, the disc is {(cx + ox, cy + oy): |ox| <= hw[|oy|], |oy| <= R}; R = 4 gives hw =
+ * [4, 3, 3, 2, 0], 49 pixels. `detections` is the union of the discs of all keypoints of the image,
+ * `matches` that of the matched ones; per image I = popcount(matches & detections), U = popcount(matches |
+ * detections), both computed as written.
+ * Deviations: OpenCV is not part of the reference snapshot, so the disc and the rounding are
+ * this library's reading of OpenCV 4, pinned by the tables of DESIGN.md §4; a keypoint with a non-finite
+ * coordinate, or one whose centre lies beyond 2^30, paints nothing (cvRound is undefined there).
+ *
+ * Kind 0, overlapFraction(A, B): over the non-empty images of each frame, M = {non-zero ids of A} n {those
+ * of B}; a keypoint is matched iff its id is in M. M empty: exactly 0.0 (the counts are still those
+ * painted). Else per side overlap = sum I / sum U by plain IEEE division and the result is (o_B < o_A) ? o_B
+ * : o_A (std::min). Keypoints of an empty image take no part (:2922). A and B need the same image count;
+ * A = B is allowed.
+ * Kind 1, the "other frames" loop of doWeNeedANewKeyframe (:1245-1280): only B is painted, a keypoint of B
+ * is matched iff its id is non-zero and among the ids of A (all images of A, :1219); the result is sum I /
+ * sum U of B as it falls.
+ * Kind 2, its current-frame part (:1202-1231): frame A alone, matched iff id != 0; sum I / sum U.
+ * n_keypoints serves the caller's `< 7 * numFrames` test.
+ * Kind 3, trackingQuality: frame A alone, matched iff flag != 0 (the caller evaluates "the landmark exists
+ * and is observed from another frame", :282-291). Per image pointArea = int(radius * radius * pi) with the
+ * untruncated double radius, I += max(0, popcount(matches) - pointArea), U += G_r G_c - pointArea; the
+ * result is matchedPoints < 8 ? 0.0 : I / U with matchedPoints the flagged keypoints of the frame.
+ * 0 / 0 gives the quiet NaN 0xFFF8000000000000, the result of that division on x86-64.
+ *
+ * Groups (optional): group_begin is a CSR over the jobs in job order. group_best = the last job of the
+ * group whose overlap is >= the running best (starting at 0.0 and updated by it): the `>=` of
+ * mostOverlappedStateId; a NaN never qualifies; -1 for an empty or all-NaN group. group_max = the fold m =
+ * (m < v) ? v : m from 0.0 (std::max of :1279).
+ *
+ * Every output may be NULL. n_jobs = 0, frames without images and images without keypoints are valid.
+ * Independent of the problem set with okvisgpu_set_problems (needs none, leaves the device parameter sets
+ * alone); uses the context's device and stream and returns with the results in the caller's arrays. A
+ * job's result does not depend on the rest of the batch and is the same bits on every run.
+ * OKVISGPU_ERR_INVALID_ARGUMENT, before anything is launched or written, for a NULL ctx, batch or result,
+ * a missing array, a negative count, a CSR not starting at 0 or not monotone, group_begin beyond n_jobs, a
+ * negative rows or cols, a frame index out of range, an unknown kind, kind 0 with differing image counts,
+ * kind 3 without flag, a factor that is not finite and >= 0, a radius above
+ * OKVISGPU_OVERLAP_MAX_RADIUS, an image whose grid needs more than OKVISGPU_OVERLAP_MASK_WORDS 32-bit
+ * words per mask (G_r * ceil(G_c / 32); both masks of an image live in 64 KiB of LDS), and between
+ * okvisgpu_solve_begin and _solve_end; okvisgpu_last_error names the offender. OKVISGPU_ERR_DEVICE if an
+ * id table ran out of slots (a frame's table holds the smallest power of two >= two slots per keypoint, so
+ * it cannot). */
+#define OKVISGPU_OVERLAP_MASK_WORDS 8192
+#define OKVISGPU_OVERLAP_MAX_RADIUS 1024
+typedef struct okvisgpu_frame_overlap_batch {
+  int32_t n_frames;
+  const int32_t* image_begin;       /* [n_frames+1] CSR into the image arrays                      */
+  const int32_t* rows;              /* [n_images] full resolution                                  */
+  const int32_t* cols;              /* [n_images]                                                  */
+  const int32_t* kp_begin;          /* [n_images+1] CSR into the keypoint arrays                   */
+  const float* keypoint;            /* [n_kp][2] cv::KeyPoint::pt (x, y)                           */
+  const uint64_t* landmark;         /* [n_kp] landmarkId, 0 = none                                 */
+  const uint8_t* flag;              /* [n_kp] or NULL; kind 3                                      */
+  int32_t n_jobs;
+  const int32_t* job_kind;          /* [n_jobs] 0..3                                               */
+  const int32_t* job_frame_a;       /* [n_jobs]                                                    */
+  const int32_t* job_frame_b;       /* [n_jobs] kinds 0 and 1 (NULL when there are none)           */
+  const double* job_radius_factor;  /* [n_jobs] kptradius_ / kptrad                                */
+  int32_t n_groups;
+  const int32_t* group_begin;       /* [n_groups+1] CSR into the jobs, or NULL with n_groups = 0   */
+} okvisgpu_frame_overlap_batch;
+
+typedef struct okvisgpu_frame_overlap_result {  /* caller-owned, any may be NULL */
+  double* overlap;                  /* [n_jobs]                                                    */
+  int32_t* count;                   /* [n_jobs][4] I, U of side A, I, U of side B; unpainted: 0    */
+  int32_t* n_matched;               /* [n_jobs][2] matched keypoints per side                      */
+  int32_t* n_keypoints;             /* [n_jobs] keypoints of frame A, all images                   */
+  int32_t* group_best;              /* [n_groups] a job index or -1                                */
+  double* group_max;                /* [n_groups]                                                  */
+} okvisgpu_frame_overlap_result;
+int okvisgpu_frame_overlap(okvisgpu_ctx* ctx, const okvisgpu_frame_overlap_batch* batch,
+                           okvisgpu_frame_overlap_result* result);
+
 /* ---------------------------------------------------------------- map matching
  * (An addition to ABI 6: a new entry point and two new structs; OKVISGPU_ABI_VERSION stays 6.)
  * The matching of Frontend::matchToMap (okvis_frontend/src/Frontend.cpp:1299-1741) on the GPU: the

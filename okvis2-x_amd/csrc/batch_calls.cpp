@@ -434,6 +434,161 @@ int okvisgpu_voxel_downsample(okvisgpu_ctx* c, const okvisgpu_voxel_downsample_b
   });
 }
 
+int okvisgpu_frame_overlap(okvisgpu_ctx* c, const okvisgpu_frame_overlap_batch* A, okvisgpu_frame_overlap_result* R) {
+  if (!c || !A || !R) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "frame_overlap: bad arguments");
+  if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "frame_overlap: call after solve_end");
+  if (A->n_frames < 0 || A->n_jobs < 0 || A->n_groups < 0)
+    return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "frame_overlap: negative count");
+  return guarded(c, [&]() {
+    const std::string who = "frame_overlap: ";
+    const size_t nf = (size_t)A->n_frames, nj = (size_t)A->n_jobs, ng = (size_t)A->n_groups;
+    if (nf && !A->image_begin) throw ArgError{who + "image_begin missing"};
+    if (nf) checkCsr(A->image_begin, nf, "image_begin", "frame", who);
+    const size_t ni = nf ? (size_t)A->image_begin[nf] : 0;
+    if (ni && (!A->rows || !A->cols || !A->kp_begin)) throw ArgError{who + "image arrays missing"};
+    if (ni) checkCsr(A->kp_begin, ni, "kp_begin", "image", who);
+    const size_t nk = ni ? (size_t)A->kp_begin[ni] : 0;
+    if (nk && (!A->keypoint || !A->landmark)) throw ArgError{who + "keypoint arrays missing"};
+    if (nj && (!A->job_kind || !A->job_frame_a || !A->job_radius_factor)) throw ArgError{who + "job arrays missing"};
+    if (ng && !A->group_begin) throw ArgError{who + "group_begin missing"};
+    if (ng) checkCsr(A->group_begin, ng, "group_begin", "group", who);
+    if (ng && (size_t)A->group_begin[ng] > nj) throw ArgError{who + "group_begin exceeds n_jobs"};
+    // the grid of every image
+    std::vector<int32_t> gr(ni), gc(ni), imgFrame(ni);
+    std::vector<uint8_t> imgLive(ni);
+    for (size_t f = 0; f < nf; ++f)
+      for (int32_t im = A->image_begin[f]; im < A->image_begin[f + 1]; ++im) imgFrame[(size_t)im] = (int32_t)f;
+    for (size_t im = 0; im < ni; ++im) {
+      if (A->rows[im] < 0 || A->cols[im] < 0) throw ArgError{who + "negative rows or cols of image " + std::to_string(im)};
+      gr[im] = A->rows[im] / 10;
+      gc[im] = A->cols[im] / 10;
+      imgLive[im] = A->rows[im] > 0 && A->cols[im] > 0;
+      if ((size_t)gr[im] * (size_t)((gc[im] + 31) / 32) > (size_t)OKVISGPU_OVERLAP_MASK_WORDS)
+        throw ArgError{who + "image " + std::to_string(im) + ": a " + std::to_string(gr[im]) + " x " + std::to_string(gc[im]) +
+                       " grid needs more than OKVISGPU_OVERLAP_MASK_WORDS words per mask"};
+    }
+    // the items, and one half-width table per distinct radius
+    std::vector<OverlapItem> items;
+    std::vector<int32_t> hw, hwOff((size_t)OKVISGPU_OVERLAP_MAX_RADIUS + 1, -1);
+    auto tableOf = [&](int32_t Rad) {
+      if (hwOff[(size_t)Rad] < 0) {
+        hwOff[(size_t)Rad] = (int32_t)hw.size();
+        hw.resize(hw.size() + (size_t)Rad + 1, 0);
+        int32_t* h = hw.data() + hwOff[(size_t)Rad];
+        int err = 0, dx = Rad, dy = 0, plus = 1, minus = 2 * Rad - 1;
+        while (dx >= dy) {  // the midpoint recurrence of OpenCV's Circle()
+          h[dy] = std::max(h[dy], dx);
+          h[dx] = std::max(h[dx], dy);
+          ++dy;
+          err += plus;
+          plus += 2;
+          if (err > 0) {
+            err -= minus;
+            --dx;
+            minus -= 2;
+          }
+        }
+      }
+      return hwOff[(size_t)Rad];
+    };
+    int32_t maxWords = 1;
+    std::vector<int32_t> nKeypoints(nj, 0);
+    for (size_t j = 0; j < nj; ++j) {
+      const std::string job = who + "job " + std::to_string(j);
+      const int32_t kind = A->job_kind[j], fa = A->job_frame_a[j];
+      if (kind < 0 || kind > 3) throw ArgError{job + ": unknown kind " + std::to_string(kind)};
+      if (fa < 0 || fa >= A->n_frames) throw ArgError{job + ": frame_a " + std::to_string(fa) + " out of range"};
+      int32_t fb = -1;
+      if (kind <= 1) {
+        if (!A->job_frame_b) throw ArgError{who + "job_frame_b missing"};
+        fb = A->job_frame_b[j];
+        if (fb < 0 || fb >= A->n_frames) throw ArgError{job + ": frame_b " + std::to_string(fb) + " out of range"};
+      }
+      if (kind == 0 && A->image_begin[fa + 1] - A->image_begin[fa] != A->image_begin[fb + 1] - A->image_begin[fb])
+        throw ArgError{job + ": frames " + std::to_string(fa) + " and " + std::to_string(fb) + " differ in image count"};
+      if (kind == 3 && !A->flag) throw ArgError{job + ": kind 3 needs flag"};
+      const double factor = A->job_radius_factor[j];
+      if (!(std::isfinite(factor) && factor >= 0.0)) throw ArgError{job + ": radius factor is not finite and >= 0"};
+      nKeypoints[j] = ni ? A->kp_begin[A->image_begin[fa + 1]] - A->kp_begin[A->image_begin[fa]] : 0;
+      for (int side = (kind == 1 ? 1 : 0); side <= (kind <= 1 ? 1 : 0); ++side) {
+        const int32_t f = side ? fb : fa;
+        for (int32_t im = A->image_begin[f]; im < A->image_begin[f + 1]; ++im) {
+          if (kind == 0 && !imgLive[(size_t)im]) continue;  // (:2922)
+          const double radius = (double)std::min(gr[(size_t)im], gc[(size_t)im]) * factor;
+          if (!(radius < (double)OKVISGPU_OVERLAP_MAX_RADIUS + 1.0))
+            throw ArgError{job + ": radius above OKVISGPU_OVERLAP_MAX_RADIUS on image " + std::to_string(im)};
+          const int32_t Rad = (int32_t)radius;
+          const double area = radius * radius * 3.14159265358979323846;  // M_PI; < 2^22
+          const int32_t other = kind == 0 ? (side ? fa : fb) : (kind == 1 ? fa : -1);
+          items.push_back({(int32_t)j, side, im, other, kind, Rad, tableOf(Rad), (int32_t)area});
+          maxWords = std::max(maxWords, gr[(size_t)im] * ((gc[(size_t)im] + 31) / 32));
+        }
+      }
+    }
+    if (!nj) {  // nothing to paint: every group is empty
+      if (R->group_best) std::fill(R->group_best, R->group_best + ng, -1);
+      if (R->group_max) std::fill(R->group_max, R->group_max + ng, 0.0);
+      return (int)OKVISGPU_OK;
+    }
+    // one id table per frame: the smallest power of two >= two slots per keypoint
+    std::vector<int32_t> tabBegin(nf + 1, 0);
+    for (size_t f = 0; f < nf; ++f) {
+      const size_t kf = ni ? (size_t)(A->kp_begin[A->image_begin[f + 1]] - A->kp_begin[A->image_begin[f]]) : 0;
+      size_t size = 2;
+      while (size < 2 * kf) size *= 2;
+      if ((size_t)tabBegin[f] + size > (size_t)0x7fffffff) throw ArgError{who + "too many keypoints"};
+      tabBegin[f + 1] = tabBegin[f] + (int32_t)size;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    OverlapDev D{};
+    D.n_kp = (int32_t)nk;
+    D.n_items = (int32_t)items.size();
+    D.n_jobs = A->n_jobs;
+    D.n_groups = A->n_groups;
+    D.table_total = tabBegin[nf];
+    D.max_words = maxWords;
+    BatchLayout S;
+    S.in(D.kp_begin, ni ? A->kp_begin : kEmptyCsr, ni + 1);
+    const auto kpImage = S.in(D.kp_image, nullptr, nk);
+    S.in(D.kp, A->keypoint, 2 * nk);
+    S.in(D.lm, A->landmark, nk);
+    if (A->flag) S.in(D.flag, A->flag, nk);
+    S.in(D.img_frame, imgFrame.data(), ni);
+    S.in(D.img_gr, gr.data(), ni);
+    S.in(D.img_gc, gc.data(), ni);
+    S.in(D.img_live, imgLive.data(), ni);
+    S.in(D.tab_begin, tabBegin.data(), nf + 1);
+    S.in(D.items, items.data(), items.size());
+    S.in(D.hw, hw.data(), hw.size());
+    S.in(D.job_kind, A->job_kind, nj);
+    if (ng) S.in(D.group_begin, A->group_begin, ng + 1);
+    // delivered below, once the error word is known to be clear
+    const auto overlap = S.out(D.overlap, nullptr, nj);
+    const auto count = S.out(D.count, nullptr, 4 * nj);
+    const auto matched = S.out(D.n_matched, nullptr, 2 * nj);
+    const auto best = S.out(D.group_best, nullptr, ng);
+    const auto gmax = S.out(D.group_max, nullptr, ng);
+    const auto err = S.out(D.err, nullptr, 1);
+    S.scratch(D.table, (size_t)D.table_total);
+    S.scratch(D.live, (size_t)D.table_total);
+    c->beginBatch(S);
+    for (size_t im = 0; im < ni; ++im)  // the image of every keypoint
+      for (int32_t k = A->kp_begin[im]; k < A->kp_begin[im + 1]; ++k) S.host(kpImage)[k] = (int32_t)im;
+    c->uploadBatch(S);
+    launch_frame_overlap(D, c->stream);
+    HIPCHK(hipGetLastError());
+    c->finishBatch(S);
+    if (*S.host(err)) throw std::runtime_error("frame_overlap: id table exhausted");
+    if (R->overlap) std::memcpy(R->overlap, S.host(overlap), sizeof(double) * nj);
+    if (R->count) std::memcpy(R->count, S.host(count), sizeof(int32_t) * 4 * nj);
+    if (R->n_matched) std::memcpy(R->n_matched, S.host(matched), sizeof(int32_t) * 2 * nj);
+    if (R->n_keypoints) std::copy(nKeypoints.begin(), nKeypoints.end(), R->n_keypoints);
+    if (R->group_best && ng) std::memcpy(R->group_best, S.host(best), sizeof(int32_t) * ng);
+    if (R->group_max && ng) std::memcpy(R->group_max, S.host(gmax), sizeof(double) * ng);
+    return (int)OKVISGPU_OK;
+  });
+}
+
 int okvisgpu_match_to_map(okvisgpu_ctx* c, const okvisgpu_match_batch* A, okvisgpu_match_result* R) {
   if (!c || !A || !R) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_to_map: bad arguments");
   if (c->inSolve) return fail(c, OKVISGPU_ERR_INVALID_ARGUMENT, "match_to_map: call after solve_end");

@@ -127,6 +127,44 @@ struct VoxelDev {
   int32_t* err;
 };
 void launch_voxel_downsample(const VoxelDev& V, hipStream_t s);
+// ViSlamBackend::overlapFraction / trackingQuality and Frontend::doWeNeedANewKeyframe for a batch of jobs
+// (kernels_overlap.hip; okvisgpu_frame_overlap). An item is one (job, side, image) whose two masks one
+// workgroup paints in LDS: `other` = the frame whose id table decides "matched" (kind 0: the other
+// side's, kind 1: frame A's, else unused), hw_off = the start of the half-width table of the item's R
+// in hw (R + 1 entries), area = the pointArea of kind 3. kp_image [n_kp] = the image of every keypoint,
+// img_frame / img_gr / img_gc / img_live [n_images] = its frame, grid rows, grid columns and whether it
+// is non-empty, tab_begin [n_frames + 1] = the frame's region of table / live (a power of two of slots).
+// The kernels write every element of table, live, count, n_matched, overlap, group_best, group_max and
+// err [1] (non-zero: a probe ran out of slots); max_words = the largest G_r * ceil(G_c / 32) of an item.
+struct OverlapItem {
+  int32_t job, side, image, other, kind, R, hw_off, area;
+};
+struct OverlapDev {
+  int32_t n_kp, n_items, n_jobs, n_groups, table_total, max_words;
+  const int32_t* kp_begin;
+  const int32_t* kp_image;
+  const float* kp;
+  const uint64_t* lm;
+  const uint8_t* flag;
+  const int32_t* img_frame;
+  const int32_t* img_gr;
+  const int32_t* img_gc;
+  const uint8_t* img_live;
+  const int32_t* tab_begin;
+  const OverlapItem* items;
+  const int32_t* hw;
+  const int32_t* job_kind;
+  const int32_t* group_begin;
+  unsigned long long* table;
+  uint8_t* live;
+  int32_t* count;
+  int32_t* n_matched;
+  double* overlap;
+  int32_t* group_best;
+  double* group_max;
+  int32_t* err;
+};
+void launch_frame_overlap(const OverlapDev& V, hipStream_t s);
 // host-evaluated factors: gather the evaluation points (host_in), scatter the uploaded results
 // (host_out) into the linearisation records; the host step between them is the runtime's
 void launch_host_gather(const DevProblem& P, int mode, hipStream_t s);

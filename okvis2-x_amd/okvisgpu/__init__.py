@@ -235,6 +235,20 @@ class VoxelDownsampleResult(C.Structure):
     _fields_ = [("keep", _up), ("n_kept", _ip)]
 
 
+class FrameOverlapBatch(C.Structure):
+    """okvisgpu_frame_overlap_batch: frames (images with keypoints and landmark ids) and the overlap jobs over them."""
+    _fields_ = [("n_frames", C.c_int32), ("image_begin", _ip), ("rows", _ip), ("cols", _ip), ("kp_begin", _ip),
+                ("keypoint", _fp), ("landmark", C.POINTER(C.c_uint64)), ("flag", _up), ("n_jobs", C.c_int32),
+                ("job_kind", _ip), ("job_frame_a", _ip), ("job_frame_b", _ip), ("job_radius_factor", _dp),
+                ("n_groups", C.c_int32), ("group_begin", _ip)]
+
+
+class FrameOverlapResult(C.Structure):
+    """okvisgpu_frame_overlap_result: the caller-owned outputs of okvisgpu_frame_overlap (any may be NULL)."""
+    _fields_ = [("overlap", _dp), ("count", _ip), ("n_matched", _ip), ("n_keypoints", _ip), ("group_best", _ip),
+                ("group_max", _dp)]
+
+
 class MatchBatch(C.Structure):
     """okvisgpu_match_batch: one map and the jobs (camera image x pass) matched against it."""
     _fields_ = [("n_poses", C.c_int32), ("poses", _dp), ("n_cameras", C.c_int32), ("cameras", C.POINTER(Camera)),
@@ -337,6 +351,7 @@ EXPORTED_SYMBOLS = [
     "okvisgpu_twopose_extrinsics_compute", "okvisgpu_twopose_extrinsics_evaluate", "okvisgpu_gauss_newton_step",
     "okvisgpu_match_to_map", "okvisgpu_plan_assembly", "okvisgpu_match_frames", "okvisgpu_place_match",
     "okvisgpu_place_refine", "okvisgpu_lidar_deskew", "okvisgpu_voxel_downsample", "okvisgpu_gps_evaluate",
+    "okvisgpu_frame_overlap",
 ]
 N_PHASES = 15
 TWOPOSE_MAX_CAMERAS = 6
@@ -408,6 +423,7 @@ def lib():
         L.okvisgpu_lidar_deskew.argtypes = [C.c_void_p, C.POINTER(LidarDeskewBatch), C.POINTER(LidarDeskewResult)]
         L.okvisgpu_voxel_downsample.argtypes = [C.c_void_p, C.POINTER(VoxelDownsampleBatch),
                                                 C.POINTER(VoxelDownsampleResult)]
+        L.okvisgpu_frame_overlap.argtypes = [C.c_void_p, C.POINTER(FrameOverlapBatch), C.POINTER(FrameOverlapResult)]
         L.okvisgpu_match_to_map.argtypes = [C.c_void_p, C.POINTER(MatchBatch), C.POINTER(MatchResult)]
         L.okvisgpu_match_frames.argtypes = [C.c_void_p, C.POINTER(FrameMatchBatch), C.POINTER(FrameMatchResult)]
         L.okvisgpu_place_match.argtypes = [C.c_void_p, C.POINTER(PlaceMatchBatch), C.POINTER(PlaceMatchResult)]
@@ -735,6 +751,32 @@ def voxel_downsample_batch(cloud_begin, point, voxel_size, use=None):
     b = VoxelDownsampleBatch()
     b.n_clouds = len(k["cloud_begin"]) - 1
     _set_arrays(b, k)
+    return b, k
+
+
+def frame_overlap_batch(image_begin, rows, cols, kp_begin, keypoint, landmark, job_kind, job_frame_a, job_frame_b,
+                        job_radius_factor, flag=None, group_begin=None):
+    """An okvisgpu_frame_overlap_batch over numpy arrays (copied to the struct's types where they differ):
+    (struct, arrays it points into). `keypoint` [n_kp, 2] float32 (cv::KeyPoint::pt), `landmark` [n_kp]
+    uint64 (0 = none), `flag` [n_kp] or None = NULL (kind 3 needs it), `job_frame_b` None = NULL (no job of
+    kind 0 or 1), `group_begin` [n_groups + 1] or None = no groups."""
+    i4 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    k = {"image_begin": i4(image_begin), "rows": i4(rows), "cols": i4(cols), "kp_begin": i4(kp_begin),
+         "keypoint": np.ascontiguousarray(keypoint, dtype=np.float32).reshape(-1, 2), "job_kind": i4(job_kind),
+         "job_frame_a": i4(job_frame_a),
+         "job_radius_factor": np.ascontiguousarray(job_radius_factor, dtype=np.float64).reshape(-1)}
+    if job_frame_b is not None:
+        k["job_frame_b"] = i4(job_frame_b)
+    if flag is not None:
+        k["flag"] = np.ascontiguousarray(flag, dtype=np.uint8).reshape(-1)
+    if group_begin is not None:
+        k["group_begin"] = i4(group_begin)
+    b = FrameOverlapBatch()
+    b.n_frames, b.n_jobs = len(k["image_begin"]) - 1, len(k["job_kind"])
+    b.n_groups = len(k["group_begin"]) - 1 if group_begin is not None else 0
+    _set_arrays(b, k)
+    k["landmark"] = np.ascontiguousarray(landmark, dtype=np.uint64).reshape(-1)
+    b.landmark = k["landmark"].ctypes.data_as(C.POINTER(C.c_uint64))
     return b, k
 
 
@@ -1161,6 +1203,21 @@ class Context:
         r = VoxelDownsampleResult()
         _set_arrays(r, out)
         self._check(lib().okvisgpu_voxel_downsample(self.h, C.byref(batch), C.byref(r)), "okvisgpu_voxel_downsample")
+        return out
+
+    def frame_overlap(self, batch: FrameOverlapBatch, fill=None):
+        """okvisgpu_frame_overlap (ViSlamBackend::overlapFraction / trackingQuality and both parts of
+        Frontend::doWeNeedANewKeyframe) for a batch built by frame_overlap_batch(): dict of overlap [n_jobs],
+        count [n_jobs, 4] (I, U of side A, I, U of side B), n_matched [n_jobs, 2], n_keypoints [n_jobs],
+        group_best [n_groups] (a job index or -1) and group_max [n_groups]. `fill` (a dict of per-output
+        values) pre-fills the arrays the call writes into."""
+        nj, ng = batch.n_jobs, batch.n_groups
+        spec = {"overlap": ((nj,), np.float64), "count": ((nj, 4), np.int32), "n_matched": ((nj, 2), np.int32),
+                "n_keypoints": ((nj,), np.int32), "group_best": ((ng,), np.int32), "group_max": ((ng,), np.float64)}
+        out = {k: np.full(shape, (fill or {}).get(k, 0), dtype=dt) for k, (shape, dt) in spec.items()}
+        r = FrameOverlapResult()
+        _set_arrays(r, out)
+        self._check(lib().okvisgpu_frame_overlap(self.h, C.byref(batch), C.byref(r)), "okvisgpu_frame_overlap")
         return out
 
     def match_to_map(self, batch: MatchBatch, fill=None):
