@@ -71,11 +71,16 @@ static __device__ unsigned int g_imuDone;
   }
 #define ICLK_COUNT(i, cond) \
   if (cond) atomicAdd(&g_imuClk[i], 1ull);
+// (the clock state handed to an inlined section of the kernel: imuResidualJacobian)
+#define ICLK_PARAMS , unsigned long long &iclk, unsigned long long(&iacc)[16]
+#define ICLK_ARGS , iclk, iacc
 #else
 #define ICLK_INIT
 #define ICLK(i)
 #define ICLK_COUNT(i, cond)
 #define ICLK_END
+#define ICLK_PARAMS
+#define ICLK_ARGS
 #endif
 
 // ---- k_lm_visit<1> (-DOKG_LMV_CLOCK): thread 0 of every workgroup adds its s_memrealtime ticks per

@@ -179,16 +179,15 @@ struct DevProblem {
   double* part_S;                  // [n_part][36]
   // extrinsic visits (variable extrinsics only): per (landmark, variable camera) the landmark's
   // observations through that camera; threads nvg.. of their landmark group (k_lm_visit<.., true>)
-  int32_t n_xvisit;
-  const int32_t* xvisit_pose;      // [n_xvisit] pose-kind block of the extrinsics
+  int32_t n_xvisit, n_pe;          // (n_pe: the cross blocks below; here, where the alignment left room)
+  const int32_t* xvisit_pose;     // [n_xvisit] pose-kind block of the extrinsics
   const int32_t* xvisit_lm;        // [n_xvisit]
   const int32_t* xvisit_obs_begin; // [n_xvisit+1] CSR into xvisit_obs
   const int32_t* xvisit_obs;       // global observation indices
   const int32_t* xvisit_slot;      // [n_xvisit] segment slot within the group
   const int32_t* lmg_xbegin;       // [n_lmg+1] extrinsic visits of group g
-  // pose-extrinsics cross blocks (k_pose_extr): per (free state pose, variable camera)
-  int32_t n_pe;
-  const int32_t* pe_pose;          // [n_pe] state pose
+  // pose-extrinsics cross blocks (k_pose_extr): n_pe of them, per (free state pose, variable camera)
+  const int32_t* pe_pose;         // [n_pe] state pose
   const int32_t* pe_ext;           // [n_pe] pose-kind block of the extrinsics
   const int32_t* pe_obs_begin;     // [n_pe+1] CSR into pe_obs
   const int32_t* pe_obs;
@@ -213,6 +212,10 @@ struct DevProblem {
   double* imu_cost[2];             // [n_fac]
   double* imu_H;                   // [n_fac][kImuHess] of the linearisation lin[lcur] (k_imu_hess)
   double* imu_jv;                  // [3][n_fac]
+  // one byte per factor wavefront (four factors), written by k_eval_imu_steady in every launch and
+  // read by k_eval_imu<false> behind it: 1 = a live factor of the wavefront redoes its
+  // preintegration. A context-owned buffer outside the arena table, like asm_rec
+  uint8_t* imu_wave_redo;          // [(n_imu + 3) / 4]
   const int32_t* win_host_range;   // [n_win][2] host factors of the window (global factor indices)
   double* host_in;                 // [n_host][kHostIn] gathered evaluation points (k_host_gather)
   double* host_out;                // [n_host][kHostOut] host results, uploaded (k_host_scatter)

@@ -13,6 +13,9 @@
 //                sum P = sum sigma^2 dP/dsigma), a square-root information factor of P
 //                (PseudoInverse.hpp:132-158; see the note above the kernel), then residual +
 //                minimal Jacobians (ImuError.cpp:861-1000).
+//  k_eval_imu_steady  launched in front of k_eval_imu<false>: takes the decision, evaluates the
+//                wavefronts none of whose factors redoes its preintegration (residual + Jacobians
+//                only) and tells k_eval_imu<false> per wavefront whether it is left to do.
 //  k_eval_priors one thread per PoseError / SpeedAndBiasError (PoseError.cpp:73-125,
 //                SpeedAndBiasError.cpp:67-101).
 //
@@ -114,27 +117,6 @@ __global__ __launch_bounds__(256) void k_eval_obs(const DevProblem* __restrict__
 // ------------------------------------------------------------------------------------ IMU
 namespace {
 
-struct ImuPre {  // preintegrated quantities (ImuError.hpp:273-304), register resident per lane
-  Q dq;
-  double Ci[9], Cdi[9], ai[3], adi[3], dadbg[9], dvdbg[9], dpdbg[9];
-};
-
-template <typename Ptr>
-__device__ __forceinline__ void loadPre(Ptr s, ImuPre& p) {
-  p.dq = Q{s[2], s[3], s[4], s[5]};
-  for (int i = 0; i < 9; ++i) {
-    p.Ci[i] = s[6 + i];
-    p.Cdi[i] = s[15 + i];
-    p.dadbg[i] = s[30 + i];
-    p.dvdbg[i] = s[39 + i];
-    p.dpdbg[i] = s[48 + i];
-  }
-  for (int i = 0; i < 3; ++i) {
-    p.ai[i] = s[24 + i];
-    p.adi[i] = s[27 + i];
-  }
-}
-
 // ---- k_eval_imu: one 16-lane group per ImuError, four factors per wavefront
 //
 // Lane l of a group owns column l of the preintegration covariance P (l < 15). Per integration
@@ -159,9 +141,6 @@ constexpr int kImuK = 4;      // integration steps per chunk (batches)
 constexpr int kImuFewChunkWindows = 2;
 #ifndef OKG_IMU_FEW_K
 #define OKG_IMU_FEW_K 16  // (build knob for A/B measurements)
-#endif
-#ifndef OKG_IMU_JAC_ROWS
-#define OKG_IMU_JAC_ROWS 1  // (build knob: 0 forms the Jacobian by columns)
 #endif
 #ifndef OKG_IMU_FREG
 #define OKG_IMU_FREG 1  // (build knob: 0 reads F_delta from LDS in both products of a step)
@@ -272,12 +251,219 @@ __device__ void groupJacobi(double* A, double* V, double* rot, int l, bool need)
 #define OKG_IMU_OCC 2
 #endif
 // (development-only phase clock of k_eval_imu: ICLK_INIT / ICLK / ICLK_END, dev_clock.hpp)
+
+// The window test of an IMU factor (evalSelect restated branch-free on the loaded WinState fields)
+// and the parameter set / linearisation buffer it evaluates. One source for evalImuBlock and
+// k_eval_imu_steady.
+template <bool APPEND>
+__device__ __forceinline__ bool imuLive(bool inR, int mode, int flR, int sDone, int sCand, int sX, int sL, int& xs,
+                                        int& lb) {
+  xs = APPEND ? 0 : (mode == 1 ? 1 - sX : sX);
+  lb = APPEND ? 0 : (mode == 1 ? 1 - sL : sL);
+  return inR && (APPEND || ((sDone == 0) & (mode != 1 || sCand != 0) & !((flR & 2) && mode < 2)));
+}
+// The re-preintegration decision (ImuError.cpp:833-859) from the stored counter, flag and reference
+// bias and the gyro bias of the evaluation point; returns doRedo. One source, as imuLive.
+template <bool APPEND>
+__device__ __forceinline__ bool imuDoRedo(double st0, double st1, const double (&bref)[6], double bg0, double bg1,
+                                          double bg2, int nSamples, int redoAlways, int& redoCounter, bool& redo) {
+  redoCounter = (int)st0;
+  redo = st1 != 0.0;
+  {
+    const double d0 = bg0 - bref[0], d1 = bg1 - bref[1], d2 = bg2 - bref[2];
+    redo = redo || (sqrt(d0 * d0 + d1 * d1 + d2 * d2) > 0.0003);
+  }
+  return APPEND || (redo && (nSamples < 50 || redoAlways)) || redoCounter == 0;
+}
+
+// Residual, cost and minimal Jacobians of one factor by its 16-lane group, from the square-root
+// information U (U(k): entry k of the lane's row l), the preintegration (state[2..56]), the four
+// parameter blocks and Delta_b. One source for every kernel that evaluates an ImuError: state, p0, p1,
+// sb0, sb1 and parp are pointers to global memory (evalImuBlock) or to a staged copy in LDS
+// (k_eval_imu_steady). sB: 90 doubles of the group's LDS; uniform control flow over the workgroup
+// (one wavefront). STAGE: the rows of J go through sJ (450 doubles of the group's LDS) and are
+// stored lane-contiguous instead of 30 eight-byte stores per lane at a 240-byte stride; without it
+// sJ is unused (the kernels of few windows and of the chain keep the direct stores).
+template <bool STAGE, typename UF, typename SP, typename PP, typename GP>
+__device__ __forceinline__ void imuResidualJacobian(const DevProblem& P, UF U, double* sB, double* sJ, SP state, PP p0,
+                                                    PP p1, PP sb0, PP sb1, const double (&Db)[6], bool success,
+                                                    bool live, int lb, int f, int l, double Dt, GP parp ICLK_PARAMS) {
+  // the preintegrated quantities (ImuError.hpp:273-304; state[2..56]), read where they are used
+  const struct {
+    SP Ci, Cdi, ai, adi, dvdbg, dpdbg;
+  } pre = {state + 6, state + 15, state + 24, state + 27, state + 39, state + 48};
+  double dadbg[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) dadbg[i] = state[30 + i];
+
+  // ---- residual and minimal Jacobians (ImuError.cpp:861-1000)
+  // The ten distinct 3x3 blocks of [F0 | F1] are staged in LDS (sB, row-major 3x3 each):
+  //  0 C_S0_W  1 C_S0_W[dp]x  2 F0(3,3)  3 C_S0_W[dv]x  4 dp_db_g  5 F0(3,9)  6 dv_db_g
+  //  7 C_doubleintegral  8 C_integral  9 F1(3,3)
+  const Q q0 = qnormalize(Q{p0[3], p0[4], p0[5], p0[6]});
+  const Q q1 = qnormalize(Q{p1[3], p1[4], p1[5], p1[6]});
+  const Q q1i = qinv(q1);
+  double err[15];
+  Q Dq;
+  {
+    double C0[9];
+    qrot(q0, C0);  // C_WS_0 ; C_S0_W = C0^T
+    double dp[3], dv[3];
+    const double gW[3] = {0.0, 0.0, parp[6]};
+    for (int k = 0; k < 3; ++k) {
+      dp[k] = p0[k] - p1[k] + sb0[k] * Dt - 0.5 * gW[k] * Dt * Dt;
+      dv[k] = sb0[k] - sb1[k] - gW[k] * Dt;
+    }
+    double adb[3];
+    mv3(dadbg, Db, adb);
+    Dq = qmul(deltaQ(-adb[0], -adb[1], -adb[2]), Q{state[2], state[3], state[4], state[5]});
+    double t0v[3], t6v[3];
+    mtv3(C0, dp, t0v);
+    mtv3(C0, dv, t6v);
+    const Q qe = qmul(Dq, qmul(q1i, q0));
+    for (int k = 0; k < 3; ++k) {
+      const double e0 = pre.dpdbg[k * 3 + 0] * Db[0] + pre.dpdbg[k * 3 + 1] * Db[1] + pre.dpdbg[k * 3 + 2] * Db[2] -
+                        (pre.Cdi[k * 3 + 0] * Db[3] + pre.Cdi[k * 3 + 1] * Db[4] + pre.Cdi[k * 3 + 2] * Db[5]);
+      const double e6 = pre.dvdbg[k * 3 + 0] * Db[0] + pre.dvdbg[k * 3 + 1] * Db[1] + pre.dvdbg[k * 3 + 2] * Db[2] -
+                        (pre.Ci[k * 3 + 0] * Db[3] + pre.Ci[k * 3 + 1] * Db[4] + pre.Ci[k * 3 + 2] * Db[5]);
+      err[k] = t0v[k] + pre.adi[k] + e0;
+      err[6 + k] = t6v[k] + pre.ai[k] + e6;
+    }
+    err[3] = 2 * qe.x; err[4] = 2 * qe.y; err[5] = 2 * qe.z;
+    for (int k = 0; k < 6; ++k) err[9 + k] = sb0[3 + k] - sb1[3 + k];
+    if (!success)
+      for (int k = 0; k < 15; ++k) err[k] = 0.0;
+    if (live && l == 0) {
+      double dpx[9], dvx[9];
+      crossMx(dp, dpx);
+      crossMx(dv, dvx);
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+          sB[0 * 9 + r * 3 + c] = C0[c * 3 + r];
+          sB[1 * 9 + r * 3 + c] = C0[0 * 3 + r] * dpx[0 * 3 + c] + C0[1 * 3 + r] * dpx[1 * 3 + c] + C0[2 * 3 + r] * dpx[2 * 3 + c];
+          sB[3 * 9 + r * 3 + c] = C0[0 * 3 + r] * dvx[0 * 3 + c] + C0[1 * 3 + r] * dvx[1 * 3 + c] + C0[2 * 3 + r] * dvx[2 * 3 + c];
+        }
+      for (int i = 0; i < 9; ++i) {
+        sB[4 * 9 + i] = pre.dpdbg[i];
+        sB[6 * 9 + i] = pre.dvdbg[i];
+        sB[7 * 9 + i] = pre.Cdi[i];
+        sB[8 * 9 + i] = pre.Ci[i];
+      }
+    }
+  }
+  if (live && l == 1) {
+    double Pm[16], Om[16], R[9];
+    qplusM(qmul(Dq, q1i), Pm);
+    qoplusM(q0, Om);
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        double s = 0;
+        for (int k = 0; k < 4; ++k) s += Pm[r * 4 + k] * Om[k * 4 + c];
+        sB[2 * 9 + r * 3 + c] = s;  // F0(3,3)
+      }
+    qoplusM(qmul(q1i, q0), Pm);
+    qoplusM(Dq, Om);
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        double s = 0;
+        for (int k = 0; k < 4; ++k) s += Pm[r * 4 + k] * Om[k * 4 + c];
+        R[r * 3 + c] = s;
+      }
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c)
+        sB[5 * 9 + r * 3 + c] = -(R[r * 3 + 0] * dadbg[0 * 3 + c] + R[r * 3 + 1] * dadbg[1 * 3 + c] +
+                                  R[r * 3 + 2] * dadbg[2 * 3 + c]);  // F0(3,9)
+  }
+  if (live && l == 2) {
+    double Pd[16], O0[16], P1i[16], T4[16];
+    qplusM(Dq, Pd);
+    qoplusM(q0, O0);
+    qplusM(q1i, P1i);
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) {
+        double s = 0;
+        for (int k = 0; k < 4; ++k) s += Pd[r * 4 + k] * O0[k * 4 + c];
+        T4[r * 4 + c] = s;
+      }
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        double s = 0;
+        for (int k = 0; k < 4; ++k) s += T4[r * 4 + k] * P1i[k * 4 + c];
+        sB[9 * 9 + r * 3 + c] = -s;  // F1(3,3)
+      }
+  }
+  const size_t fl = live ? (size_t)f : 0;
+  const auto lin = gmemw(P.imu_lin[lb] + fl * kImuLin);
+  double rr = 0.0;
+  if (live && l < 15) {
+#pragma unroll
+    for (int k = 0; k < 15; ++k) rr += U(k) * err[k];
+    lin[l] = rr;
+  }
+  const double c2 = groupSum(l < 15 ? rr * rr : 0.0);
+  if (live && l == 0) gmemw(P.imu_cost[lb])[f] = 0.5 * c2;
+  __syncthreads();
+  ICLK(4)
+  // J = U [F0 | F1]. Column j of [F0 | F1] has at most three non-zero 3-blocks: (block row, staged
+  // block, sign, or identity); the table depends on j only.
+  // Lane l < 15 forms row l of J: U's row l in registers, the 30 columns unrolled (the column
+  // table a compile-time constant), the staged blocks read as LDS broadcasts; a lane's 30 stores
+  // are contiguous.
+  if (live && l < 15) {
+    double u[15];
+#pragma unroll
+    for (int k = 0; k < 15; ++k) u[k] = U(k);
+#pragma unroll
+    for (int j = 0; j < 30; ++j) {
+      const bool right = j >= 15;
+      const int jj = right ? j - 15 : j, bj = jj / 3, c = jj % 3;
+      int nt = 0, trow[3] = {0, 0, 0}, tblk[3] = {0, 0, 0};
+      double tsc[3] = {0.0, 0.0, 0.0};
+      auto add = [&](int row, int blk, double sc) { trow[nt] = row; tblk[nt] = blk; tsc[nt] = sc; ++nt; };
+      if (!right) {
+        if (bj == 0) add(0, 0, 1.0);
+        else if (bj == 1) { add(0, 1, 1.0); add(3, 2, 1.0); add(6, 3, 1.0); }
+        else if (bj == 2) { add(0, 0, Dt); add(6, 0, 1.0); }
+        else if (bj == 3) { add(0, 4, 1.0); add(3, 5, 1.0); add(6, 6, 1.0); }
+        else { add(0, 7, -1.0); add(6, 8, -1.0); }
+      } else {
+        if (bj == 0) add(0, 0, -1.0);
+        else if (bj == 1) add(3, 9, 1.0);
+        else if (bj == 2) add(6, 0, -1.0);
+      }
+      const int idrow = (bj >= 3) ? 3 * bj + c : -1;
+      const double idv = right ? -1.0 : 1.0;
+      double acc = 0.0;
+      if (success) {
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+          if (t < nt) {
+            const double* Bk = sB + tblk[t] * 9;
+            acc += tsc[t] * (u[trow[t]] * Bk[0 * 3 + c] + u[trow[t] + 1] * Bk[1 * 3 + c] + u[trow[t] + 2] * Bk[2 * 3 + c]);
+          }
+        if (idrow >= 0) acc += idv * u[idrow];
+      }
+      if (STAGE) sJ[l * 30 + j] = acc;
+      else lin[15 + l * 30 + j] = acc;
+    }
+  }
+  if (STAGE) {  // the rows from LDS, lane-contiguous: a group stores 128 bytes in a row per instruction
+    __syncthreads();
+    if (live)
+      for (int e = l; e < 450; e += kImuGroup) lin[15 + e] = sJ[e];
+  }
+  ICLK(5)
+}
+
 // APPEND: ImuError::append (ImuError.cpp:63-255) for a batch of factors (okvisgpu_imu_append): the
 // chain starts from the stored state (Delta_q, integrals, cross_, dv_db_g, P) at imu_t0 (= the old
 // t1), integrates the appended samples with the eliminated state's bias (sb[0] row blk[1]) up to
 // imu_t1, and writes the state and the new square-root information; no residual.
 __device__ __noinline__ void evalPriorsThread(const DevProblem& P, int t, int mode);
-template <bool APPEND, int K = kImuK>
+// GATED (k_eval_imu<false>, launched behind k_eval_imu_steady): a wavefront whose byte of
+// imu_wave_redo is 0 was evaluated there and returns at once; one whose byte is 1 finds its inputs as
+// they were before that launch.
+template <bool APPEND, int K = kImuK, bool GATED = false>
 __device__ __forceinline__ void evalImuBlock(const DevProblem& P, int mode, int bid) {
   using LY = ImuLds<K>;
   if (!APPEND) {  // the trailing workgroups: priors and pose-graph edges (uniform per workgroup)
@@ -287,6 +473,7 @@ __device__ __forceinline__ void evalImuBlock(const DevProblem& P, int mode, int 
       return;
     }
   }
+  if (GATED && gmem(P.imu_wave_redo)[bid] == 0) return;
   const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
   const int f = bid * kImuPerWG + g;
   ICLK_INIT
@@ -329,9 +516,9 @@ __device__ __forceinline__ void evalImuBlock(const DevProblem& P, int mode, int 
   const int nTot = gmem(P.imu_sbegin)[P.n_imu];  // samples of the batch (bounds of the cache warm-up)
   asm volatile("" ::"v"(flR), "v"(blkR.y), "v"(t0), "v"(t1), "v"(st0), "v"(st1), "v"(bref[0]), "v"(bref[5]),
                "v"(sDone), "v"(sCand), "v"(sX), "v"(sL), "v"(tsLast));
-  const bool live = inR && (APPEND || ((sDone == 0) & (mode != 1 || sCand != 0) & !((flR & 2) && mode < 2)));
+  int xs, lb;
+  const bool live = imuLive<APPEND>(inR, mode, flR, sDone, sCand, sX, sL, xs, lb);
   const int w = APPEND ? 0 : wR;
-  const int xs = APPEND ? 0 : (mode == 1 ? 1 - sX : sX), lb = APPEND ? 0 : (mode == 1 ? 1 - sL : sL);
   const int fs = live ? f : 0;  // safe index for idle groups (writes are all under live)
 
   const auto blk = gmem(P.imu_blocks + 4 * fs);
@@ -339,14 +526,10 @@ __device__ __forceinline__ void evalImuBlock(const DevProblem& P, int mode, int 
   const auto state = gmemw(P.imu_state + (size_t)fs * kImuState);
 
   // ---- re-preintegration decision (ImuError.cpp:833-859)
-  int redoCounter = (int)st0;
-  bool redo = st1 != 0.0;
-  {
-    const double d0 = sb0[3] - bref[0], d1 = sb0[4] - bref[1], d2 = sb0[5] - bref[2];
-    redo = redo || (sqrt(d0 * d0 + d1 * d1 + d2 * d2) > 0.0003);
-  }
-  const bool doRedo =
-      APPEND || (redo && ((send - sbeg) < 50 || P.opt.redo_propagation_always)) || redoCounter == 0;
+  int redoCounter;
+  bool redo;
+  const bool doRedo = imuDoRedo<APPEND>(st0, st1, bref, sb0[3], sb0[4], sb0[5], send - sbeg,
+                                        P.opt.redo_propagation_always, redoCounter, redo);
   // redoPreintegration returns -1 before touching any state when the samples do not cover t1
   // (ImuError.cpp:270-273): the old preintegration is kept.
   const bool covered = (send > sbeg) && tsLast >= t1;
@@ -833,213 +1016,134 @@ __device__ __forceinline__ void evalImuBlock(const DevProblem& P, int mode, int 
   const auto p0 = gmem(pick2(xs, P.pose[0], P.pose[1]) + 7 * (size_t)blk[0]);
   const auto p1 = gmem(pick2(xs, P.pose[0], P.pose[1]) + 7 * (size_t)blk[2]);
   const auto sb1 = gmem(pick2(xs, P.sb[0], P.sb[1]) + 9 * (size_t)blk[3]);
-  ImuPre pre;
-  loadPre(state, pre);
   const bool success = live && (!integrate || steps > 0);
   if (live && l == 0) {
     state[0] = (double)redoCounter;
     state[1] = redo ? 1.0 : 0.0;
     if (doRedo && !covered) state[291] = -1.0;  // what redoPreintegration returned (ImuError.cpp:272)
   }
-
-  // ---- residual and minimal Jacobians (ImuError.cpp:861-1000)
-  // The ten distinct 3x3 blocks of [F0 | F1] are staged in LDS (sB, row-major 3x3 each):
-  //  0 C_S0_W  1 C_S0_W[dp]x  2 F0(3,3)  3 C_S0_W[dv]x  4 dp_db_g  5 F0(3,9)  6 dv_db_g
-  //  7 C_doubleintegral  8 C_integral  9 F1(3,3)
-  const Q q0 = qnormalize(Q{p0[3], p0[4], p0[5], p0[6]});
-  const Q q1 = qnormalize(Q{p1[3], p1[4], p1[5], p1[6]});
-  const Q q1i = qinv(q1);
-  const double Dt = durToSec(t1 - t0);
-  double err[15];
-  Q Dq;
-  {
-    double C0[9];
-    qrot(q0, C0);  // C_WS_0 ; C_S0_W = C0^T
-    double dp[3], dv[3];
-    const double gW[3] = {0.0, 0.0, parp[6]};
-    for (int k = 0; k < 3; ++k) {
-      dp[k] = p0[k] - p1[k] + sb0[k] * Dt - 0.5 * gW[k] * Dt * Dt;
-      dv[k] = sb0[k] - sb1[k] - gW[k] * Dt;
-    }
-    double adb[3];
-    mv3(pre.dadbg, Db, adb);
-    Dq = qmul(deltaQ(-adb[0], -adb[1], -adb[2]), pre.dq);
-    double t0v[3], t6v[3];
-    mtv3(C0, dp, t0v);
-    mtv3(C0, dv, t6v);
-    const Q qe = qmul(Dq, qmul(q1i, q0));
-    for (int k = 0; k < 3; ++k) {
-      const double e0 = pre.dpdbg[k * 3 + 0] * Db[0] + pre.dpdbg[k * 3 + 1] * Db[1] + pre.dpdbg[k * 3 + 2] * Db[2] -
-                        (pre.Cdi[k * 3 + 0] * Db[3] + pre.Cdi[k * 3 + 1] * Db[4] + pre.Cdi[k * 3 + 2] * Db[5]);
-      const double e6 = pre.dvdbg[k * 3 + 0] * Db[0] + pre.dvdbg[k * 3 + 1] * Db[1] + pre.dvdbg[k * 3 + 2] * Db[2] -
-                        (pre.Ci[k * 3 + 0] * Db[3] + pre.Ci[k * 3 + 1] * Db[4] + pre.Ci[k * 3 + 2] * Db[5]);
-      err[k] = t0v[k] + pre.adi[k] + e0;
-      err[6 + k] = t6v[k] + pre.ai[k] + e6;
-    }
-    err[3] = 2 * qe.x; err[4] = 2 * qe.y; err[5] = 2 * qe.z;
-    for (int k = 0; k < 6; ++k) err[9 + k] = sb0[3 + k] - sb1[3 + k];
-    if (!success)
-      for (int k = 0; k < 15; ++k) err[k] = 0.0;
-    if (live && l == 0) {
-      double dpx[9], dvx[9];
-      crossMx(dp, dpx);
-      crossMx(dv, dvx);
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {
-          sB[0 * 9 + r * 3 + c] = C0[c * 3 + r];
-          sB[1 * 9 + r * 3 + c] = C0[0 * 3 + r] * dpx[0 * 3 + c] + C0[1 * 3 + r] * dpx[1 * 3 + c] + C0[2 * 3 + r] * dpx[2 * 3 + c];
-          sB[3 * 9 + r * 3 + c] = C0[0 * 3 + r] * dvx[0 * 3 + c] + C0[1 * 3 + r] * dvx[1 * 3 + c] + C0[2 * 3 + r] * dvx[2 * 3 + c];
-        }
-      for (int i = 0; i < 9; ++i) {
-        sB[4 * 9 + i] = pre.dpdbg[i];
-        sB[6 * 9 + i] = pre.dvdbg[i];
-        sB[7 * 9 + i] = pre.Cdi[i];
-        sB[8 * 9 + i] = pre.Ci[i];
-      }
-    }
-  }
-  if (live && l == 1) {
-    double Pm[16], Om[16], R[9];
-    qplusM(qmul(Dq, q1i), Pm);
-    qoplusM(q0, Om);
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) {
-        double s = 0;
-        for (int k = 0; k < 4; ++k) s += Pm[r * 4 + k] * Om[k * 4 + c];
-        sB[2 * 9 + r * 3 + c] = s;  // F0(3,3)
-      }
-    qoplusM(qmul(q1i, q0), Pm);
-    qoplusM(Dq, Om);
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) {
-        double s = 0;
-        for (int k = 0; k < 4; ++k) s += Pm[r * 4 + k] * Om[k * 4 + c];
-        R[r * 3 + c] = s;
-      }
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c)
-        sB[5 * 9 + r * 3 + c] = -(R[r * 3 + 0] * pre.dadbg[0 * 3 + c] + R[r * 3 + 1] * pre.dadbg[1 * 3 + c] +
-                                  R[r * 3 + 2] * pre.dadbg[2 * 3 + c]);  // F0(3,9)
-  }
-  if (live && l == 2) {
-    double Pd[16], O0[16], P1i[16], T4[16];
-    qplusM(Dq, Pd);
-    qoplusM(q0, O0);
-    qplusM(q1i, P1i);
-    for (int r = 0; r < 4; ++r)
-      for (int c = 0; c < 4; ++c) {
-        double s = 0;
-        for (int k = 0; k < 4; ++k) s += Pd[r * 4 + k] * O0[k * 4 + c];
-        T4[r * 4 + c] = s;
-      }
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) {
-        double s = 0;
-        for (int k = 0; k < 4; ++k) s += T4[r * 4 + k] * P1i[k * 4 + c];
-        sB[9 * 9 + r * 3 + c] = -s;  // F1(3,3)
-      }
-  }
-  const size_t fl = live ? (size_t)f : 0;
-  const auto lin = gmemw(P.imu_lin[lb] + fl * kImuLin);
-  double rr = 0.0;
-  if (live && l < 15) {
-    for (int k = 0; k < 15; ++k) rr += sA[l * kS + k] * err[k];
-    lin[l] = rr;
-  }
-  const double c2 = groupSum(l < 15 ? rr * rr : 0.0);
-  if (live && l == 0) gmemw(P.imu_cost[lb])[f] = 0.5 * c2;
-  __syncthreads();
-  ICLK(4)
-  // J = U [F0 | F1]. Column j of [F0 | F1] has at most three non-zero 3-blocks: (block row, staged
-  // block, sign, or identity); the table depends on j only.
-#if OKG_IMU_JAC_ROWS
-  // Lane l < 15 forms row l of J: U's row l in registers, the 30 columns unrolled (the column
-  // table a compile-time constant), the staged blocks read as LDS broadcasts; every entry is the
-  // same expression as in the column form (same bits), and a lane's 30 stores are contiguous.
-  if (live && l < 15) {
-    double u[15];
-#pragma unroll
-    for (int k = 0; k < 15; ++k) u[k] = sA[l * kS + k];
-#pragma unroll
-    for (int j = 0; j < 30; ++j) {
-      const bool right = j >= 15;
-      const int jj = right ? j - 15 : j, bj = jj / 3, c = jj % 3;
-      int nt = 0, trow[3] = {0, 0, 0}, tblk[3] = {0, 0, 0};
-      double tsc[3] = {0.0, 0.0, 0.0};
-      auto add = [&](int row, int blk, double sc) { trow[nt] = row; tblk[nt] = blk; tsc[nt] = sc; ++nt; };
-      if (!right) {
-        if (bj == 0) add(0, 0, 1.0);
-        else if (bj == 1) { add(0, 1, 1.0); add(3, 2, 1.0); add(6, 3, 1.0); }
-        else if (bj == 2) { add(0, 0, Dt); add(6, 0, 1.0); }
-        else if (bj == 3) { add(0, 4, 1.0); add(3, 5, 1.0); add(6, 6, 1.0); }
-        else { add(0, 7, -1.0); add(6, 8, -1.0); }
-      } else {
-        if (bj == 0) add(0, 0, -1.0);
-        else if (bj == 1) add(3, 9, 1.0);
-        else if (bj == 2) add(6, 0, -1.0);
-      }
-      const int idrow = (bj >= 3) ? 3 * bj + c : -1;
-      const double idv = right ? -1.0 : 1.0;
-      double acc = 0.0;
-      if (success) {
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-          if (t < nt) {
-            const double* Bk = sB + tblk[t] * 9;
-            acc += tsc[t] * (u[trow[t]] * Bk[0 * 3 + c] + u[trow[t] + 1] * Bk[1 * 3 + c] + u[trow[t] + 2] * Bk[2 * 3 + c]);
-          }
-        if (idrow >= 0) acc += idv * u[idrow];
-      }
-      lin[15 + l * 30 + j] = acc;
-    }
-  }
-#else
-  // (column form: lane l computes columns l and l + 16)
-  if (live) {
-    for (int pass = 0; pass < 2; ++pass) {
-      const int j = l + 16 * pass;
-      if (j >= 30) break;
-      const bool right = j >= 15;
-      const int jj = right ? j - 15 : j, bj = jj / 3, c = jj % 3;
-      int nt = 0, trow[3], tblk[3];
-      double tsc[3];
-      auto add = [&](int row, int blk, double sc) { trow[nt] = row; tblk[nt] = blk; tsc[nt] = sc; ++nt; };
-      if (!right) {
-        if (bj == 0) add(0, 0, 1.0);
-        else if (bj == 1) { add(0, 1, 1.0); add(3, 2, 1.0); add(6, 3, 1.0); }
-        else if (bj == 2) { add(0, 0, Dt); add(6, 0, 1.0); }
-        else if (bj == 3) { add(0, 4, 1.0); add(3, 5, 1.0); add(6, 6, 1.0); }
-        else { add(0, 7, -1.0); add(6, 8, -1.0); }
-      } else {
-        if (bj == 0) add(0, 0, -1.0);
-        else if (bj == 1) add(3, 9, 1.0);
-        else if (bj == 2) add(6, 0, -1.0);
-      }
-      // identity / minus-identity blocks on the bias rows
-      const int idrow = (bj >= 3) ? 3 * bj + c : -1;
-      const double idv = right ? -1.0 : 1.0;
-      for (int i = 0; i < 15; ++i) {
-        double acc = 0.0;
-        if (success) {
-          for (int t = 0; t < nt; ++t) {
-            const double* Bk = sB + tblk[t] * 9;
-            const double* Ui = sA + i * kS + trow[t];
-            acc += tsc[t] * (Ui[0] * Bk[0 * 3 + c] + Ui[1] * Bk[1 * 3 + c] + Ui[2] * Bk[2 * 3 + c]);
-          }
-          if (idrow >= 0) acc += idv * sA[i * kS + idrow];
-        }
-        lin[15 + i * 30 + j] = acc;
-      }
-    }
-  }
-#endif
-  ICLK(5)
+  imuResidualJacobian<false>(P, [&](int k) { return sA[l * kS + k]; }, sB, nullptr, state, p0, p1, sb0, sb1, Db, success,
+                             live, lb, f, l, durToSec(t1 - t0), parp ICLK_ARGS);
   ICLK_END
 }
 
 template <bool APPEND>
 __global__ __launch_bounds__(64, OKG_IMU_OCC) void k_eval_imu(const DevProblem* __restrict__ Pp, int mode) {
-  evalImuBlock<APPEND>(*Pp, mode, (int)blockIdx.x);
+  evalImuBlock<APPEND, kImuK, !APPEND>(*Pp, mode, (int)blockIdx.x);
+}
+
+// ---- k_eval_imu_steady: the wavefronts none of whose factors re-integrates (every one, once the
+// biases have settled), launched by launch_eval_imu in front of k_eval_imu<false> on the same stream.
+// Same mapping (a 16-lane group per factor, wavefront b serves factors 4b .. 4b + 3), none of the
+// chain's LDS or registers; its LDS holds the staged inputs (1.4 KB per group) and the rows of J on
+// their way to lane-contiguous stores (3.6 KB per group).
+//
+// Everything a factor's evaluation reads is requested in two rounds with clamped indices and
+// consumed before the first test (dependent load levels): with the factor's record the
+// head of its state, the lane's row of U (registers; no LDS transfer) and the lanes' shares of the
+// preintegration; with the window's state the lanes' shares of p0 | sb0 | p1 | sb1 from BOTH
+// parameter sets (which one is evaluated follows from the window's state, loaded in the same round).
+// The shares go to LDS, from where imuResidualJacobian reads them as broadcasts.
+//
+// The decision is taken here once per evaluation (imuDoRedo) and handed to k_eval_imu<false> as one
+// byte per wavefront, imu_wave_redo[b] = any live factor of b redoes its preintegration: the split is
+// on doRedo, not on `integrate` (resetDb, state[0], state[1] and state[291] = -1 follow doRedo also
+// where the samples do not cover t1), and the byte is written for every wavefront of every launch.
+// With the byte 1 nothing else is written here. With 0 the live factors are evaluated as
+// evalImuBlock does without a redo: Delta_b = sb0[3 + k] - state[60 + k], state[0] and state[1]
+// (the flag may rise without a redo: a factor of 50 samples or more).
+#ifndef OKG_IMU_STEADY_STAGE
+#define OKG_IMU_STEADY_STAGE 1  // (build knob: 0 stores the rows of J directly, as evalImuBlock does)
+#endif
+struct ImuSteadyLds {  // per group, doubles: the ten staged blocks | state[2..56] | p0 | sb0 | p1 | sb1 | g | J
+  static constexpr int blocks = 0, pre = 90, op = pre + 55, par = op + 32, jac = par + 1,
+                       total = jac + (OKG_IMU_STEADY_STAGE ? 450 : 0);
+};
+static_assert(ImuSteadyLds::total * 8 * kImuPerWG <= 20480, "LDS for eight workgroups (two waves per SIMD) per CU");
+// Waves per SIMD asked of the compiler. The residual and Jacobian section as it stands (the ten
+// blocks staged by lanes 0..2, four 4x4 quaternion matrices live in one lane) needs 236 VGPRs:
+// at 3 and 4 waves it spills (100 / 154 VGPRs) and the step is no faster / slower than without
+// this kernel (profiles/imu_steady_ab.txt), so the kernel runs at two waves and no scratch.
+// (Staging by five or eleven lanes brought it to 204 / 202 VGPRs and no measurable gain: dropped.)
+#ifndef OKG_IMU_STEADY_OCC
+#define OKG_IMU_STEADY_OCC 2  // (build knob for A/B measurements)
+#endif
+__global__ __launch_bounds__(64, OKG_IMU_STEADY_OCC) void k_eval_imu_steady(const DevProblem* __restrict__ Pp, int mode) {
+  const DevProblem& P = *Pp;
+  const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+  const int f = (int)blockIdx.x * kImuPerWG + g;
+  ICLK_INIT
+  __shared__ double sAll[kImuPerWG][ImuSteadyLds::total];
+  double* sB = sAll[g] + ImuSteadyLds::blocks;
+  double* sPre = sAll[g] + ImuSteadyLds::pre;
+  double* sOp = sAll[g] + ImuSteadyLds::op;
+  double* sPar = sAll[g] + ImuSteadyLds::par;
+
+  // round 1: the record, the state's head, row min(l, 14) of U and entries 2 + l + 16 i of the state
+  const bool inR = f < P.n_imu;
+  const int fc = inR ? f : 0;
+  const int wR = gmem(P.imu_win)[fc];
+  const int flR = gmem(P.imu_flags)[fc];
+  const int4 blkR = gmem(reinterpret_cast<const int4*>(P.imu_blocks))[fc];
+  const int64_t t0 = gmem(P.imu_t0)[fc], t1 = gmem(P.imu_t1)[fc];
+  const int sbeg = gmem(P.imu_sbegin)[fc], send = gmem(P.imu_sbegin)[fc + 1];
+  const auto stR = gmem(P.imu_state + (size_t)fc * kImuState);
+  const double st0 = stR[0], st1 = stR[1];
+  double bref[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) bref[k] = stR[57 + 3 + k];
+  double ur[15];
+#pragma unroll
+  for (int k = 0; k < 15; ++k) ur[k] = stR[66 + 15 * min(l, 14) + k];
+  double pr[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) pr[i] = stR[2 + min(l + 16 * i, 54)];
+  // round 2: the window's state and gravity; element l of p0 | sb0 and of p1 | sb1 (7 + 9 = 16)
+  const auto gst = gmem(P.st + wR);
+  const int sDone = gst->done, sCand = gst->eval_cand, sX = gst->xcur, sL = gst->lcur;
+  const double gz = gmem(P.imu_par + 7 * wR)[6];
+  double opv[2][2];  // [parameter set][first / second block pair]
+#pragma unroll
+  for (int x = 0; x < 2; ++x) {
+    const double* pose = x ? P.pose[1] : P.pose[0];
+    const double* sb = x ? P.sb[1] : P.sb[0];
+    opv[x][0] = l < 7 ? gmem(pose)[7 * (size_t)blkR.x + l] : gmem(sb)[9 * (size_t)blkR.y + (l - 7)];
+    opv[x][1] = l < 7 ? gmem(pose)[7 * (size_t)blkR.z + l] : gmem(sb)[9 * (size_t)blkR.w + (l - 7)];
+  }
+  asm volatile("" ::"v"(flR), "v"(t0), "v"(t1), "v"(send), "v"(st0), "v"(st1), "v"(bref[0]), "v"(bref[5]), "v"(ur[0]),
+               "v"(ur[14]), "v"(pr[0]), "v"(pr[3]), "v"(sDone), "v"(sCand), "v"(sX), "v"(sL), "v"(gz), "v"(opv[0][0]),
+               "v"(opv[0][1]), "v"(opv[1][0]), "v"(opv[1][1]));
+  int xs, lb;
+  const bool live = imuLive<false>(inR, mode, flR, sDone, sCand, sX, sL, xs, lb);
+  sOp[l] = xs ? opv[1][0] : opv[0][0];
+  sOp[16 + l] = xs ? opv[1][1] : opv[0][1];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) sPre[min(l + 16 * i, 54)] = pr[i];  // (the clamped lanes write entry 54's own value)
+  if (l == 0) sPar[0] = gz;
+  __syncthreads();  // (the workgroup is one wavefront)
+  const double* p0 = sOp;
+  const double* sb0 = sOp + 7;
+  const double* p1 = sOp + 16;
+  const double* sb1 = sOp + 23;
+
+  int redoCounter;
+  bool redo;
+  const bool doRedo = imuDoRedo<false>(st0, st1, bref, sb0[3], sb0[4], sb0[5], send - sbeg,
+                                       P.opt.redo_propagation_always, redoCounter, redo);
+  const bool heavy = __any(live && doRedo) != 0;
+  if (threadIdx.x == 0) gmemw(P.imu_wave_redo)[blockIdx.x] = heavy ? 1 : 0;
+  if (heavy) return;  // uniform: k_eval_imu<false> runs this wavefront as before
+
+  double Db[6];
+  for (int k = 0; k < 6; ++k) Db[k] = sb0[3 + k] - bref[k];
+  if (live && l == 0) {
+    const auto state = gmemw(P.imu_state + (size_t)f * kImuState);
+    state[0] = (double)redoCounter;
+    state[1] = redo ? 1.0 : 0.0;
+  }
+  imuResidualJacobian<OKG_IMU_STEADY_STAGE != 0>(P, [&](int k) { return ur[k]; }, sB, sAll[g] + ImuSteadyLds::jac, sPre - 2,
+                                                 p0, p1, sb0, sb1, Db, live, live, lb, f, l, durToSec(t1 - t0),
+                                                 sPar - 6 ICLK_ARGS);
 }
 // Few windows: the observations (64 per workgroup), then the IMU factors, priors and edges, as one
 // launch (one graph node fewer on a single window's latency chain). K: steps per IMU chunk
@@ -1245,7 +1349,9 @@ void launch_eval_obs(const DevProblem& P, int mode, hipStream_t s) {
 // k_eval_imu's grid: the IMU factors (4 per workgroup), then the priors and edges (64 per workgroup)
 void launch_eval_imu(const DevProblem& P, int mode, hipStream_t s) {
   const int np = P.n_pprior + P.n_sbprior + P.n_relpose;
-  const int nb = (P.n_imu + kImuPerWG - 1) / kImuPerWG + (np + 63) / 64;
+  const int nImuWG = (P.n_imu + kImuPerWG - 1) / kImuPerWG, nb = nImuWG + (np + 63) / 64;
+  // the wavefronts without a redo, and imu_wave_redo for the others (which k_eval_imu<false> then runs)
+  if (nImuWG > 0) hipLaunchKernelGGL(k_eval_imu_steady, dim3(nImuWG), dim3(64), 0, s, P.self, mode);
   if (nb > 0) hipLaunchKernelGGL(k_eval_imu<false>, dim3(nb), dim3(64), 0, s, P.self, mode);
 }
 // The IMU factors (and priors / edges) as the solve's evaluation runs them: one or two windows

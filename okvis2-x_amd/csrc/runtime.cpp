@@ -355,6 +355,8 @@ void okvisgpu_ctx::build() {
       HIPCHK(hipMemcpyAsync(rec, B.asm_rec.data(), B.asm_rec.size() * sizeof(AsmRec), hipMemcpyHostToDevice, stream));
     P.asm_rec = static_cast<const AsmRec*>(rec);
   }
+  // k_eval_imu_steady's byte per factor wavefront (four factors each): likewise the context's own
+  P.imu_wave_redo = static_cast<uint8_t*>(imuWaveRedoBuf.need(std::max<size_t>(64, ((size_t)P.n_imu + 3) / 4)));
   HIPCHK(hipStreamSynchronize(stream));
   decideRegime(0);  // (default options: the entry points that launch without a solve_begin)
   uploadDescriptor();

@@ -202,6 +202,9 @@ struct okvisgpu_ctx {
   // the assembly work items as records (HostBatch::asm_rec, DevProblem::asm_rec): likewise outside
   // the arena table, uploaded by build(), kept until the next build
   okg::GrowBuffer asmRecBuf;
+  // DevProblem::imu_wave_redo, one byte per wavefront of IMU factors: sized by build(), written by
+  // k_eval_imu_steady in every launch before k_eval_imu<false> reads it
+  okg::GrowBuffer imuWaveRedoBuf;
 
   ~okvisgpu_ctx();
 
