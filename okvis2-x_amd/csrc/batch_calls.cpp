@@ -35,6 +35,21 @@ void checkCsr(const int32_t* begin, size_t n, const char* name, const char* item
       throw ArgError{who + name + " not monotone" + (item ? " at " + std::string(item) + " " + std::to_string(i) : "")};
 }
 
+// Item i's IMU samples cover its interval: there are some, the first is not after t_begin and, with
+// t_end given, the last is not before it (the assertions of ImuError.cpp:550, ViGraph.cpp:976-982
+// with GpsErrorAsynchronous.cpp:311-313, and LidarMotionUndistortion.cpp:34). `who` and `item` as
+// for checkCsr; nameBegin / nameEnd are the call's names of the two stamps.
+void checkCovered(const int32_t* begin, const int64_t* ts, size_t i, const char* nameBegin, int64_t t_begin,
+                  const char* nameEnd, const int64_t* t_end, const char* item, const std::string& who) {
+  const std::string it = who + item + " " + std::to_string(i);
+  const int32_t s0 = begin[i], s1 = begin[i + 1];
+  if (s1 == s0) throw ArgError{it + " has no samples"};
+  if (ts[s0] > t_begin)
+    throw ArgError{it + ": first sample " + std::to_string(ts[s0]) + " !<= " + nameBegin + " " + std::to_string(t_begin)};
+  if (t_end && ts[s1 - 1] < *t_end)
+    throw ArgError{it + ": last sample " + std::to_string(ts[s1 - 1]) + " !>= " + nameEnd + " " + std::to_string(*t_end)};
+}
+
 // The caller's cameras as rows of `doubles` values: kCamDoubles (distortion model, fu, fv, cu, cv,
 // eight coefficients) or kMatchCamDoubles (the same, then width and height).
 std::vector<double> packCameras(const okvisgpu_camera* cams, size_t n, int doubles, const std::string& who,
@@ -163,13 +178,9 @@ int okvisgpu_imu_propagate(okvisgpu_ctx* c, const okvisgpu_imu_propagate_batch* 
   return guarded(c, [&]() {
     const size_t n = (size_t)A->n;
     checkCsr(A->sample_begin, n, "sample_begin", nullptr, "imu_propagate: ");
-    for (size_t i = 0; i < n; ++i) {  // the reference's assertion (ImuError.cpp:550)
-      const int32_t s0 = A->sample_begin[i];
-      if (A->sample_begin[i + 1] == s0) throw ArgError{"imu_propagate: item " + std::to_string(i) + " has no samples"};
-      if (A->sample_t_ns[s0] > A->t_start_ns[i])
-        throw ArgError{"imu_propagate: item " + std::to_string(i) + ": first sample " + std::to_string(A->sample_t_ns[s0]) +
-                       " !<= t_start " + std::to_string(A->t_start_ns[i])};
-    }
+    for (size_t i = 0; i < n; ++i)  // (an item that ends before t_end gets steps = -1 on the device)
+      checkCovered(A->sample_begin, A->sample_t_ns, i, "t_start", A->t_start_ns[i], nullptr, nullptr, "item",
+                   "imu_propagate: ");
     HIPCHK(hipSetDevice(c->device));
     const size_t ns = (size_t)A->sample_begin[n];
     ImuPropagateDev D{};
@@ -239,17 +250,9 @@ int okvisgpu_gps_evaluate(okvisgpu_ctx* c, const okvisgpu_gps_batch* A, okvisgpu
         throw ArgError{fac + ": information is not symmetric"};
       if (!chol3U(G, U)) throw ArgError{fac + ": information is not positive definite"};
       if (!async) continue;
-      // the assertions of ViGraph.cpp:976-982 and GpsErrorAsynchronous.cpp:311-313
-      const int32_t s0 = A->sample_begin[i], s1 = A->sample_begin[i + 1];
-      if (A->t_g_ns[i] < A->t_k_ns[i])
+      if (A->t_g_ns[i] < A->t_k_ns[i])  // (ViGraph.cpp:976-982)
         throw ArgError{fac + ": t_g " + std::to_string(A->t_g_ns[i]) + " < t_k " + std::to_string(A->t_k_ns[i])};
-      if (s1 == s0) throw ArgError{fac + " has no samples"};
-      if (A->sample_t_ns[s0] > A->t_k_ns[i])
-        throw ArgError{fac + ": first sample " + std::to_string(A->sample_t_ns[s0]) + " !<= t_k " +
-                       std::to_string(A->t_k_ns[i])};
-      if (A->sample_t_ns[s1 - 1] < A->t_g_ns[i])
-        throw ArgError{fac + ": last sample " + std::to_string(A->sample_t_ns[s1 - 1]) + " !>= t_g " +
-                       std::to_string(A->t_g_ns[i])};
+      checkCovered(A->sample_begin, A->sample_t_ns, i, "t_k", A->t_k_ns[i], "t_g", &A->t_g_ns[i], "factor", who);
     }
     HIPCHK(hipSetDevice(c->device));
     GpsDev D{};
@@ -320,9 +323,8 @@ int okvisgpu_lidar_deskew(okvisgpu_ctx* c, const okvisgpu_lidar_deskew_batch* A,
       const int32_t q0 = A->query_begin[i], q1 = A->query_begin[i + 1];
       const std::string scan = who + "scan " + std::to_string(i);
       if (q1 > q0 && s1 - s0 < 2) throw ArgError{scan + " has queries but fewer than two samples"};
-      if (s1 > s0 && A->sample_t_ns[s0] > A->t_start_ns[i])  // (LidarMotionUndistortion.cpp:34)
-        throw ArgError{scan + ": first sample " + std::to_string(A->sample_t_ns[s0]) + " !<= t_start " +
-                       std::to_string(A->t_start_ns[i])};
+      if (s1 > s0)  // (a scan without queries may come without samples)
+        checkCovered(A->sample_begin, A->sample_t_ns, i, "t_start", A->t_start_ns[i], nullptr, nullptr, "scan", who);
       for (int32_t s = s0 + 1; s < s1; ++s)
         if (A->sample_t_ns[s] < A->sample_t_ns[s - 1])
           throw ArgError{scan + ": sample stamps decrease at sample " + std::to_string(s - s0)};

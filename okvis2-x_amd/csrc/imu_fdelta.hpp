@@ -1,8 +1,10 @@
-// imu_fdelta.hpp — the block-sparse F_delta of one IMU integration step and its product with a
-// 15-vector, shared by the kernels that propagate a 15x15 covariance column by column: k_eval_imu
-// (ImuError::redoPreintegration / append, kernels_eval.hip) and k_imu_propagate
-// (ImuError::propagation, kernels_imu_propagate.hip). Both recursions have the same non-identity
-// blocks (03, 06 = dt I, 09, 012, 39, 63, 69, 612); the entries differ and are the callers'.
+// imu_fdelta.hpp — the block-sparse F_delta of one IMU integration step, its product with a
+// 15-vector and the constants of the LDS exchange of P <- F P F^T, shared by the kernels that propagate a 15x15
+// covariance column by column in 16-lane groups: k_eval_imu (ImuError::redoPreintegration / append,
+// kernels_eval.hip), k_imu_propagate_group (ImuError::propagation, kernels_imu_propagate.hip) and
+// k_gps_async (GpsErrorAsynchronous::redoPreintegration, kernels_gps.hip). The recursions have the
+// same non-identity blocks (03, 06 = dt I, 09, 012, 39, 63, 69, 612); the entries are the group step's
+// (imu_chain_group_body.hpp) and k_eval_imu's own.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -48,5 +50,10 @@ __device__ __forceinline__ double groupSum(double v) {  // sum over the 16 lanes
   v += __shfl_xor(v, 1, 64);
   return v;
 }
+
+// ---- the column exchange of k_imu_propagate_group and k_gps_async: four groups per wavefront, each
+// with a 15 x kColStride tile of LDS
+constexpr int kGroupsPerWave = 4;
+constexpr int kColStride = 17;  // row stride of the LDS exchange: lanes walking a column hit distinct banks
 
 }  // namespace okg

@@ -1,6 +1,7 @@
-// imu_step.hpp — what the IMU stepping kernels share (kernels_imu_propagate.hip, kernels_lidar.hip):
-// one sample as stored with its clamped prefetch load, the inputs of one trapezoid step and the
-// step's dq (ImuError.cpp:644-650; ViInterface.cpp:696-703 is the same text).
+// imu_step.hpp — the sample and step-input layer of the IMU stepping kernels
+// (kernels_imu_propagate.hip, kernels_gps.hip, kernels_lidar.hip): one sample as stored with its
+// clamped prefetch load, the inputs of one trapezoid step and the step's dq (ImuError.cpp:644-650;
+// ViInterface.cpp:696-703 is the same text). The step on them is imu_chain.hpp's.
 #pragma once
 
 #include "okvisgpu_math.hpp"

@@ -20,8 +20,7 @@
 // A factor's arithmetic does not depend on the batch or on its position in it: loops run to the
 // wavefront's longest re-integrating factor with the others predicated off, and no lane reads another
 // factor's data. The host has refused every factor whose samples do not cover [t_k, t_g].
-#include "imu_fdelta.hpp"
-#include "imu_step.hpp"
+#include "imu_chain.hpp"
 #include "launch.hpp"
 #include "mat3_spd.hpp"
 #include "okvisgpu_math.hpp"
@@ -29,9 +28,6 @@
 namespace okg {
 
 namespace {
-
-constexpr int kGpsPerWG = 4;  // 16-lane groups per wavefront
-constexpr int kGS = 17;  // row stride of the LDS exchange: lanes walking a column hit distinct banks
 
 // C = A B for row-major A [R x K], B [K x N]
 template <int R, int K, int N>
@@ -184,8 +180,8 @@ __global__ __launch_bounds__(64) void k_gps_sync(const GpsDev A) {
 template <bool COV, int NP>
 __global__ __launch_bounds__(64) void k_gps_async(const GpsDev A) {
   const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
-  const int i = (int)blockIdx.x * kGpsPerWG + g;
-  __shared__ double sAll[kGpsPerWG][15 * kGS];
+  const int i = (int)blockIdx.x * kGroupsPerWave + g;
+  __shared__ double sAll[kGroupsPerWave][15 * kColStride];
   double* const M = sAll[g];
 
   const bool inR = i < A.n;
@@ -218,6 +214,7 @@ __global__ __launch_bounds__(64) void k_gps_async(const GpsDev A) {
 #pragma unroll
   for (int e = 0; e < 9; ++e) Ci[e] = Cdi[e] = cross[e] = dadbg[e] = dvdbg[e] = dpdbg[e] = 0.0;
   double ai[3] = {0, 0, 0}, adi[3] = {0, 0, 0};
+  [[maybe_unused]] double Dt = 0.0;  // (the step body sums it; the residual stage takes t_g - t_k)
   double Pc[NP][15];  // column l of P (NP = 1) or of the four dPdsigma (NP = 4)
 #pragma unroll
   for (int j = 0; j < NP; ++j)
@@ -266,65 +263,8 @@ __global__ __launch_bounds__(64) void k_gps_async(const GpsDev A) {
     nxt = ahead;
     double F[kFdt + 1];
     if (doStep) {
-      const double dt = s.dt;
-      double sh, ch;
-      const Q dq = stepDq(s, sh, ch);
-      Dq = qmul(Dq, dq);
-      double C1[9], CC[9], CCa[3];
-      qrot(Dq, C1);
-#pragma unroll
-      for (int e = 0; e < 9; ++e) CC[e] = C[e] + C1[e];
-      mv3(CC, s.a, CCa);
-      // Jacobian parts (:425-432): cross_1 = R(dq)^T cross + rightJacobian(w dt) dt,
-      // X = C [a]x cross + C_1 [a]x cross_1, dalpha_db_g += C_1 rightJacobian(w dt) dt
-      double X[9], C1Jr[9];
-      {
-        const double wdt[3] = {s.w[0] * dt, s.w[1] * dt, s.w[2] * dt};
-        double Jr[9], Rdqi[9], ax[9], t0[9], t1[9], cross1[9];
-        rightJacobianHalf(wdt, sh, ch, Jr);
-        mm3(C1, Jr, C1Jr);
-        qrot(qinv(dq), Rdqi);
-        crossMx(s.a, ax);
-        mm3(C, ax, t0);
-        mm3(t0, cross, X);
-        mm3(Rdqi, cross, cross1);
-#pragma unroll
-        for (int e = 0; e < 9; ++e) cross[e] = cross1[e] + Jr[e] * dt;
-        mm3(C1, ax, t0);
-        mm3(t0, cross, t1);
-#pragma unroll
-        for (int e = 0; e < 9; ++e) X[e] += t1[e];
-      }
-      const double qdt2 = 0.25 * dt * dt;
-      // F_delta (:437-452) from the sums before the step, then the sums (:416-432)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const double v = ai[j] * dt + qdt2 * CCa[j];
-        if (COV) {
-          F[kF03 + j] = v;                  // F03 = -[acc_integral dt + dt^2/4 (C + C_1) a]x, held as its vector
-          F[kF63 + j] = 0.5 * dt * CCa[j];  // F63 = -[dt/2 (C + C_1) a]x
-        }
-        adi[j] += v;
-        ai[j] += 0.5 * CCa[j] * dt;
-      }
-#pragma unroll
-      for (int e = 0; e < 9; ++e) {
-        const double p = dt * dvdbg[e] + qdt2 * X[e];
-        if (COV) {
-          F[kF09 + e] = p;
-          F[kF012 + e] = -Ci[e] * dt + qdt2 * CC[e];
-          F[kF39 + e] = -dt * C1[e];
-          F[kF69 + e] = 0.5 * dt * X[e];
-          F[kF612 + e] = -0.5 * dt * CC[e];
-        }
-        Cdi[e] += Ci[e] * dt + qdt2 * CC[e];
-        Ci[e] += 0.5 * dt * CC[e];
-        dadbg[e] += C1Jr[e] * dt;
-        dpdbg[e] += p;
-        dvdbg[e] += 0.5 * dt * X[e];
-        C[e] = C1[e];
-      }
-      if (COV) F[kFdt] = dt;
+      constexpr bool JR = true;
+#include "imu_chain_group_body.hpp"
       time = s.nexttime;
       ++steps;
       if (s.nexttime == t_g) done = true;
@@ -337,13 +277,13 @@ __global__ __launch_bounds__(64) void k_gps_async(const GpsDev A) {
           double Mc[15];
           applyF(F, Pc[j], Mc);
 #pragma unroll
-          for (int e = 0; e < 15; ++e) M[l * kGS + e] = Mc[e];
+          for (int e = 0; e < 15; ++e) M[l * kColStride + e] = Mc[e];
         }
         __syncthreads();
         if (doStep && l < 15) {
           double Mr[15];
 #pragma unroll
-          for (int e = 0; e < 15; ++e) Mr[e] = M[e * kGS + l];
+          for (int e = 0; e < 15; ++e) Mr[e] = M[e * kColStride + l];
           applyF(F, Mr, Pc[j]);
           double q;
           if (NP == 1) {
@@ -366,12 +306,12 @@ __global__ __launch_bounds__(64) void k_gps_async(const GpsDev A) {
     for (int j = 0; j < NP; ++j) {
       if (doRedo && l < 15) {
 #pragma unroll
-        for (int e = 0; e < 15; ++e) M[l * kGS + e] = Pc[j][e];
+        for (int e = 0; e < 15; ++e) M[l * kColStride + e] = Pc[j][e];
       }
       __syncthreads();
       if (doRedo && l < 15) {
 #pragma unroll
-        for (int e = 0; e < 15; ++e) Pc[j][e] = 0.5 * Pc[j][e] + 0.5 * M[e * kGS + l];
+        for (int e = 0; e < 15; ++e) Pc[j][e] = 0.5 * Pc[j][e] + 0.5 * M[e * kColStride + l];
       }
       __syncthreads();
     }
@@ -427,13 +367,13 @@ __global__ __launch_bounds__(64) void k_gps_async(const GpsDev A) {
   if (COV) {
     if (l < 6) {
 #pragma unroll
-      for (int e = 0; e < 6; ++e) M[l * kGS + e] = Pc[0][e];
+      for (int e = 0; e < 6; ++e) M[l * kColStride + e] = Pc[0][e];
     }
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < 6; ++r)
 #pragma unroll
-      for (int c = 0; c < 6; ++c) P6[r * 6 + c] = M[c * kGS + r];
+      for (int c = 0; c < 6; ++c) P6[r * 6 + c] = M[c * kColStride + r];
   }
   if (!(inR && l == 0)) return;  // (no barrier follows)
 
@@ -453,7 +393,7 @@ __global__ __launch_bounds__(64) void k_gps_async(const GpsDev A) {
   qrot(Q{G[3], G[4], G[5], G[6]}, C_GW);  // (:117-118: as stored)
 
   // T_WS at t_g with the first-order bias correction (:147-153)
-  const double Dt = durToSec(t_g - t_k);
+  const double Dtg = durToSec(t_g - t_k);
   const double gW[3] = {0.0, 0.0, A.par[6]};
   double t0[3], t1[3], inc[3], Cinc[3], rtg[3];
   mv3(dpdbg, Db, t0);
@@ -462,7 +402,7 @@ __global__ __launch_bounds__(64) void k_gps_async(const GpsDev A) {
   for (int j = 0; j < 3; ++j) inc[j] = adi[j] + t0[j] - t1[j];
   mv3(C0, inc, Cinc);
 #pragma unroll
-  for (int j = 0; j < 3; ++j) rtg[j] = pose[j] + v0[j] * Dt - 0.5 * gW[j] * Dt * Dt + Cinc[j];
+  for (int j = 0; j < 3; ++j) rtg[j] = pose[j] + v0[j] * Dtg - 0.5 * gW[j] * Dtg * Dtg + Cinc[j];
   mv3(dadbg, Db, t0);
   const Q qtg = qnormalize(qmul(qmul(q0, Dq), deltaQ(-t0[0], -t0[1], -t0[2])));
   double Ctg[9], aW[3];
@@ -532,7 +472,7 @@ __global__ __launch_bounds__(64) void k_gps_async(const GpsDev A) {
   for (int r = 0; r < 3; ++r)
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      Jsb[r * 9 + c] = -C_GW[r * 3 + c] * Dt;
+      Jsb[r * 9 + c] = -C_GW[r * 3 + c] * Dtg;
       Jsb[r * 9 + 3 + c] = -T1[r * 3 + c] - T2[r * 3 + c];
       Jsb[r * 9 + 6 + c] = B1[r * 3 + c];
     }
@@ -546,7 +486,7 @@ void launch_gps_evaluate(const GpsDev& A, hipStream_t s) {
     k_gps_sync<<<(A.n + 63) / 64, 64, 0, s>>>(A);
     return;
   }
-  const int blocks = (A.n + kGpsPerWG - 1) / kGpsPerWG;
+  const int blocks = (A.n + kGroupsPerWave - 1) / kGroupsPerWave;
   if (!A.use_cov)
     k_gps_async<false, 1><<<blocks, 64, 0, s>>>(A);
   else if (A.four_p)

@@ -17,8 +17,7 @@
 // data. An item whose samples do not reach t_end gets steps = -1 and nothing else is written
 // (:552-553); an item with no integrated step keeps its pose and speed/bias bits (Jacobian = I,
 // covariance = 0).
-#include "imu_fdelta.hpp"
-#include "imu_step.hpp"
+#include "imu_chain.hpp"
 #include "launch.hpp"
 #include "okvisgpu_math.hpp"
 
@@ -41,18 +40,6 @@ __device__ __forceinline__ PropItem loadItem(const ImuPropagateDev& A, int i) {
   // imuMeasurements.back().timeStamp >= end (:552); the host has refused N == 0
   it.covered = it.N > 0 && gmem(A.ts)[it.sbeg + max(it.N - 1, 0)] >= it.t_end;
   return it;
-}
-
-// Sample min(k, N - 1) of the item (the prefetch of imu_step.hpp, which also has PropStep and stepDq).
-__device__ __forceinline__ RawSample loadSample(const ImuPropagateDev& A, const PropItem& it, int k) {
-  return loadRawSample(A.ts, A.ga, it.sbeg, it.N, k);
-}
-// One pass of the sample loop up to the integrity check (:584-640) for sample k of an item whose
-// integration time is `time` (stepSample, imu_step.hpp): false when the sample is skipped.
-__device__ __forceinline__ bool propSample(const ImuPropagateDev& A, const PropItem& it, int k, const RawSample& cur,
-                                           const RawSample& nxt, int64_t time, bool started, const double* bg,
-                                           const double* ba, PropStep& s) {
-  return stepSample(A.par[0], A.par[1], it.N, it.t_end, k, cur, nxt, time, started, bg, ba, s);
 }
 
 // The outputs that need no Jacobian (:726-732), written by one lane: r_1, q_1 = normalize(q_0 Dq)
@@ -99,30 +86,16 @@ __global__ __launch_bounds__(64) void k_imu_propagate_lane(const ImuPropagateDev
   double ai[3] = {0, 0, 0}, adi[3] = {0, 0, 0}, Dt = 0.0;
   int64_t time = it.t_start;
   int steps = 0;
-  RawSample cur = loadSample(A, it, 0), nxt = loadSample(A, it, 1);
+  RawSample cur = loadRawSample(A.ts, A.ga, it.sbeg, it.N, 0), nxt = loadRawSample(A.ts, A.ga, it.sbeg, it.N, 1);
   for (int k = 0; k < it.N; ++k) {
-    const RawSample ahead = loadSample(A, it, k + 2);
+    const RawSample ahead = loadRawSample(A.ts, A.ga, it.sbeg, it.N, k + 2);
     PropStep s;
-    const bool ok = propSample(A, it, k, cur, nxt, time, steps > 0, bg, ba, s);
+    const bool ok = stepSample(A.par[0], A.par[1], it.N, it.t_end, k, cur, nxt, time, steps > 0, bg, ba, s);
     cur = nxt;
     nxt = ahead;
     if (!ok) continue;
-    const double dt = s.dt;
-    Dt += dt;
-    double sh, ch;
-    Dq = qmul(Dq, stepDq(s, sh, ch));
-    double C1[9], CCa[3];
-    qrot(Dq, C1);
-#pragma unroll
-    for (int e = 0; e < 9; ++e) C[e] += C1[e];
-    mv3(C, s.a, CCa);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      adi[j] += ai[j] * dt + 0.25 * CCa[j] * dt * dt;
-      ai[j] += 0.5 * CCa[j] * dt;
-    }
-#pragma unroll
-    for (int e = 0; e < 9; ++e) C[e] = C1[e];
+    Dt += s.dt;
+#include "imu_chain_lane_body.hpp"
     time = s.nexttime;
     ++steps;
     if (s.nexttime == it.t_end) break;
@@ -138,14 +111,12 @@ __global__ __launch_bounds__(64) void k_imu_propagate_lane(const ImuPropagateDev
 
 // ---- one 16-lane group per item: Jacobian, and with COV the covariance
 constexpr int kPropGroup = 16;
-constexpr int kPropPerWG = 4;
-constexpr int kPS = 17;  // row stride of the LDS exchange: lanes walking a column hit distinct banks
 
 template <bool COV>
 __global__ __launch_bounds__(64) void k_imu_propagate_group(const ImuPropagateDev A) {
   const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
-  const int i = (int)blockIdx.x * kPropPerWG + g;
-  __shared__ double sAll[kPropPerWG][15 * kPS];  // per group: the P exchange, then the Jacobian
+  const int i = (int)blockIdx.x * kGroupsPerWave + g;
+  __shared__ double sAll[kGroupsPerWave][15 * kColStride];  // per group: the P exchange, then the Jacobian
   double* const M = sAll[g];
 
   const bool inR = i < A.n;
@@ -173,75 +144,18 @@ __global__ __launch_bounds__(64) void k_imu_propagate_group(const ImuPropagateDe
   int Nmax = live ? it.N : 0;
   Nmax = max(Nmax, __shfl_xor(Nmax, 16, 64));
   Nmax = max(Nmax, __shfl_xor(Nmax, 32, 64));
-  RawSample cur = loadSample(A, it, 0), nxt = loadSample(A, it, 1);
+  RawSample cur = loadRawSample(A.ts, A.ga, it.sbeg, it.N, 0), nxt = loadRawSample(A.ts, A.ga, it.sbeg, it.N, 1);
   for (int k = 0; k < Nmax; ++k) {
-    const RawSample ahead = loadSample(A, it, k + 2);
+    const RawSample ahead = loadRawSample(A.ts, A.ga, it.sbeg, it.N, k + 2);
     PropStep s;
     const bool doStep =
-        !done && k < it.N && propSample(A, it, k, cur, nxt, time, steps > 0, bg, ba, s);  // uniform over the group
+        !done && k < it.N && stepSample(A.par[0], A.par[1], it.N, it.t_end, k, cur, nxt, time, steps > 0, bg, ba, s);  // uniform over the group
     cur = nxt;
     nxt = ahead;
     double F[kFdt + 1];
     if (doStep) {
-      const double dt = s.dt;
-      Dt += dt;
-      double sh, ch;
-      const Q dq = stepDq(s, sh, ch);
-      Dq = qmul(Dq, dq);
-      double C1[9], CC[9], CCa[3];
-      qrot(Dq, C1);
-#pragma unroll
-      for (int e = 0; e < 9; ++e) CC[e] = C[e] + C1[e];
-      mv3(CC, s.a, CCa);
-      // Jacobian parts (:663-668): cross_1 = R(dq)^T cross + rightJacobian(w dt) dt,
-      // X = C [a]x cross + C_1 [a]x cross_1
-      double X[9];
-      {
-        const double wdt[3] = {s.w[0] * dt, s.w[1] * dt, s.w[2] * dt};
-        double Jr[9], Rdqi[9], ax[9], t0[9], t1[9], cross1[9];
-        rightJacobianHalf(wdt, sh, ch, Jr);
-        qrot(qinv(dq), Rdqi);
-        crossMx(s.a, ax);
-        mm3(C, ax, t0);
-        mm3(t0, cross, X);
-        mm3(Rdqi, cross, cross1);
-#pragma unroll
-        for (int e = 0; e < 9; ++e) cross[e] = cross1[e] + Jr[e] * dt;
-        mm3(C1, ax, t0);
-        mm3(t0, cross, t1);
-#pragma unroll
-        for (int e = 0; e < 9; ++e) X[e] += t1[e];
-      }
-      const double qdt2 = 0.25 * dt * dt;
-      // F_delta (:672-682) from the sums before the step, then the sums (:656-668)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const double v = ai[j] * dt + qdt2 * CCa[j];
-        if (COV) {
-          F[kF03 + j] = v;                     // F03 = -[acc_integral dt + dt^2/4 (C + C_1) a]x, held as its vector
-          F[kF63 + j] = 0.5 * dt * CCa[j];     // F63 = -[dt/2 (C + C_1) a]x
-        }
-        adi[j] += v;
-        ai[j] += 0.5 * CCa[j] * dt;
-      }
-#pragma unroll
-      for (int e = 0; e < 9; ++e) {
-        const double p = dt * dvdbg[e] + qdt2 * X[e];
-        if (COV) {
-          F[kF09 + e] = p;
-          F[kF012 + e] = -Ci[e] * dt + qdt2 * CC[e];
-          F[kF39 + e] = -dt * C1[e];
-          F[kF69 + e] = 0.5 * dt * X[e];
-          F[kF612 + e] = -0.5 * dt * CC[e];
-        }
-        Cdi[e] += Ci[e] * dt + qdt2 * CC[e];
-        Ci[e] += 0.5 * dt * CC[e];
-        dadbg[e] += dt * C1[e];  // (no right Jacobian here, unlike redoPreintegration)
-        dpdbg[e] += p;
-        dvdbg[e] += 0.5 * dt * X[e];
-        C[e] = C1[e];
-      }
-      if (COV) F[kFdt] = dt;
+      constexpr bool JR = false;
+#include "imu_chain_group_body.hpp"
       time = s.nexttime;
       ++steps;
       if (s.nexttime == it.t_end) done = true;
@@ -252,13 +166,13 @@ __global__ __launch_bounds__(64) void k_imu_propagate_group(const ImuPropagateDe
         double Mc[15];
         applyF(F, Pc, Mc);
 #pragma unroll
-        for (int e = 0; e < 15; ++e) M[l * kPS + e] = Mc[e];
+        for (int e = 0; e < 15; ++e) M[l * kColStride + e] = Mc[e];
       }
       __syncthreads();
       if (doStep && l < 15) {
         double Mr[15];
 #pragma unroll
-        for (int e = 0; e < 15; ++e) Mr[e] = M[e * kPS + l];
+        for (int e = 0; e < 15; ++e) Mr[e] = M[e * kColStride + l];
         applyF(F, Mr, Pc);
         const double dt = s.dt;
         double sg = A.par[2], sa = A.par[3];
@@ -329,16 +243,16 @@ __global__ __launch_bounds__(64) void k_imu_propagate_group(const ImuPropagateDe
       for (int b = 0; b < 3; ++b) {
         double o[3];
         mv3(C0, Pc + 3 * b, o);
-        M[l * kPS + 3 * b] = o[0]; M[l * kPS + 3 * b + 1] = o[1]; M[l * kPS + 3 * b + 2] = o[2];
+        M[l * kColStride + 3 * b] = o[0]; M[l * kColStride + 3 * b + 1] = o[1]; M[l * kColStride + 3 * b + 2] = o[2];
       }
 #pragma unroll
-      for (int e = 9; e < 15; ++e) M[l * kPS + e] = Pc[e];
+      for (int e = 9; e < 15; ++e) M[l * kColStride + e] = Pc[e];
     }
     __syncthreads();
     if (live && l < 15) {
       double Mr[15];
 #pragma unroll
-      for (int e = 0; e < 15; ++e) Mr[e] = M[e * kPS + l];
+      for (int e = 0; e < 15; ++e) Mr[e] = M[e * kColStride + l];
       const auto Pout = gmemw(A.cov + 225 * (size_t)i + 15 * l);
 #pragma unroll
       for (int b = 0; b < 3; ++b) {
@@ -357,9 +271,9 @@ __global__ __launch_bounds__(64) void k_imu_propagate_group(const ImuPropagateDe
 void launch_imu_propagate(const ImuPropagateDev& A, hipStream_t s) {
   if (A.n <= 0) return;
   if (A.cov)
-    k_imu_propagate_group<true><<<(A.n + kPropPerWG - 1) / kPropPerWG, 64, 0, s>>>(A);
+    k_imu_propagate_group<true><<<(A.n + kGroupsPerWave - 1) / kGroupsPerWave, 64, 0, s>>>(A);
   else if (A.jac)
-    k_imu_propagate_group<false><<<(A.n + kPropPerWG - 1) / kPropPerWG, 64, 0, s>>>(A);
+    k_imu_propagate_group<false><<<(A.n + kGroupsPerWave - 1) / kGroupsPerWave, 64, 0, s>>>(A);
   else
     k_imu_propagate_lane<<<(A.n + 63) / 64, 64, 0, s>>>(A);
 }

@@ -23,7 +23,7 @@
 // no floating-point value is combined across lanes.
 #include <climits>
 
-#include "imu_step.hpp"
+#include "imu_chain.hpp"
 #include "launch.hpp"
 #include "okvisgpu_math.hpp"
 
@@ -31,16 +31,12 @@ namespace okg {
 
 namespace {
 
-// The propagator's carried state: Delta_q_, acc_integral_, acc_doubleintegral_.
-struct LidarState {
-  Q Dq;
-  double ai[3], adi[3];
-};
-
 // step(k, tau, T) for ts[k] < T <= ts[k+1] and tau < T (ViInterface.cpp:660-715): cur / nxt are the
-// samples k and k + 1, tau the end of the committed chain. Returns omega_S_true in w.
+// samples k and k + 1, tau the end of the committed chain. The interpolation rules are the
+// propagator's own (:674-691, not stepSample's); the step is the lane step of imu_chain.hpp on its carried
+// state Delta_q_, acc_integral_, acc_doubleintegral_. Returns omega_S_true in w.
 __device__ __forceinline__ void lidarStep(const RawSample& cur, const RawSample& nxt, int64_t tau, int64_t T,
-                                          const double* bg, const double* ba, LidarState& S, double* w) {
+                                          const double* bg, const double* ba, LaneChain& S, double* w) {
   double om0[3], ac0[3], om1[3], ac1[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
@@ -77,21 +73,15 @@ __device__ __forceinline__ void lidarStep(const RawSample& cur, const RawSample&
     s.a[j] = 0.5 * (ac0[j] + ac1[j]) - ba[j];
     w[j] = s.w[j];
   }
-  double sh, ch, C[9], C1[9], CCa[3];
+  double C[9];  // R(Delta_q) before the step: a table row holds Dq only
   qrot(S.Dq, C);
-  S.Dq = qmul(S.Dq, stepDq(s, sh, ch));
-  qrot(S.Dq, C1);
-#pragma unroll
-  for (int e = 0; e < 9; ++e) C[e] += C1[e];
-  mv3(C, s.a, CCa);
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    S.adi[j] += S.ai[j] * dt + 0.25 * CCa[j] * dt * dt;
-    S.ai[j] += 0.5 * CCa[j] * dt;
-  }
+  Q& Dq = S.Dq;
+  double* const ai = S.ai;
+  double* const adi = S.adi;
+#include "imu_chain_lane_body.hpp"
 }
 
-__device__ __forceinline__ void storeRow(double* table, size_t row, const LidarState& S) {
+__device__ __forceinline__ void storeRow(double* table, size_t row, const LaneChain& S) {
   const auto o = gmemw(table + (size_t)kLidarRow * row);
   o[0] = S.Dq.x; o[1] = S.Dq.y; o[2] = S.Dq.z; o[3] = S.Dq.w;
 #pragma unroll
@@ -118,7 +108,7 @@ __global__ __launch_bounds__(64) void k_lidar_chain(const LidarDeskewDev L) {
   if (N <= 0 || gmem(L.qbegin)[i + 1] == gmem(L.qbegin)[i]) return;  // no query reads a row of this scan
   const auto sbp = gmem(L.sb0 + 9 * (size_t)i);
   const double bg[3] = {sbp[3], sbp[4], sbp[5]}, ba[3] = {sbp[6], sbp[7], sbp[8]};
-  LidarState S{Q{0.0, 0.0, 0.0, 1.0}, {0, 0, 0}, {0, 0, 0}};
+  LaneChain S{Q{0.0, 0.0, 0.0, 1.0}, {0, 0, 0}, {0, 0, 0}};
   int64_t tau = gmem(L.t_start)[i];
   RawSample cur = loadRawSample(L.ts, L.ga, sbeg, N, 0), nxt = loadRawSample(L.ts, L.ga, sbeg, N, 1);
   for (int k = 0; k < N; ++k) {
@@ -165,7 +155,7 @@ __global__ __launch_bounds__(kLidarPointsWG) void k_lidar_points(const LidarDesk
     const int k = lo;  // <= N - 2
     const RawSample cur = loadRawSample(L.ts, L.ga, sbeg, N, k), nxt = loadRawSample(L.ts, L.ga, sbeg, N, k + 1);
     const auto row = gmem(L.table + (size_t)kLidarRow * ((size_t)sbeg + k));
-    LidarState S{Q{row[0], row[1], row[2], row[3]}, {row[4], row[5], row[6]}, {row[7], row[8], row[9]}};
+    LaneChain S{Q{row[0], row[1], row[2], row[3]}, {row[4], row[5], row[6]}, {row[7], row[8], row[9]}};
     const double bg[3] = {sbp[3], sbp[4], sbp[5]}, ba[3] = {sbp[6], sbp[7], sbp[8]};
     lidarStep(cur, nxt, cur.t > t0 ? cur.t : t0, T, bg, ba, S, w);
     // getState (:762-798) with Delta_b = 0

@@ -441,6 +441,20 @@ def test_gpu_crafted_batch(og, gpu_ctx, crafted, parity):
 
 
 @pytest.mark.gpu
+def test_gpu_four_matrix_recursion(og, gpu_ctx, crafted, parity, monkeypatch):
+    """6b. The same batch with OKVISGPU_GPS_FOUR_P=1 (read on every call): k_gps_async<true, 4> carries the
+    reference's four dPdsigma matrices through the recursion and the symmetrisation and sums them at the
+    end. Same contract and step counts as test_gpu_crafted_batch."""
+    monkeypatch.setenv("OKVISGPU_GPS_FOUR_P", "1")
+    args, kw, state0, index, ref, ref_state = crafted
+    state = state0.copy()
+    got = _run(og, gpu_ctx, args, kw, state)
+    _compare(parity, "crafted_four_p", got, ref, state, ref_state)
+    steps = {k: int(got["steps"][i]) for k, i in index.items()}
+    assert (steps["a"], steps["c"], steps["d"], steps["h"], steps["i"]) == (1, 0, 8, 200, 1)
+
+
+@pytest.mark.gpu
 def test_gpu_random_batch_bitwise(og, gpu_ctx, random257, parity):
     """7. 257 random factors of 2 to 45 samples: within the contract; the first 1 and the first 5 alone
     give the bits they have inside the 257; two runs give the same bits."""
